@@ -901,7 +901,9 @@ def conv_theta_tile(ext, w: torch.Tensor, atten: Optional[torch.Tensor],
     """θ = atten⊙w + aw emitted straight into the conv-tiled bf16 layout
     the hand-written conv consumes (mode 0: [C/32][9][K][32p]; mode 1: the
     flipped-transposed dgrad tile [K/32][9][C][32p]) — composition, cast
-    and im2col-free weight re-layout in ONE pass."""
+    and im2col-free weight re-layout in ONE pass.  mode 2: the same
+    flipped-transposed θ as a plain [C][3][3][K] buffer, i.e. a
+    channels-last [C, K, 3, 3] conv weight (see conv_theta_flipt)."""
     w_d = w.detach()
     assert w_d.is_contiguous(memory_format=torch.channels_last)
     k, c = w_d.shape[0], w_d.shape[1]
@@ -914,6 +916,14 @@ def conv_theta_tile(ext, w: torch.Tensor, atten: Optional[torch.Tensor],
     return out
 
 
+def conv_theta_flipt(ext, theta: torch.Tensor) -> torch.Tensor:
+    """wT[c, k, r, s] = θ[k, c, 2-r, 2-s] as a channels-last bf16 conv
+    weight: dgrad of the 3×3 s1p1 conv is conv2d(dy, wT, padding=1)."""
+    k, c = theta.shape[0], theta.shape[1]
+    flat = conv_theta_tile(ext, theta, None, None, mode=2)
+    return flat.view(c, 3, 3, k).permute(0, 3, 1, 2)
+
+
 def _conv_impl() -> str:
     """Per-op conv engine policy.  'auto' (default) picks the MEASURED
     winner per op (profiles/README.md K1 table): the library conv
@@ -922,7 +932,11 @@ def _conv_impl() -> str:
     library while keeping the fused one-pass θ production (compose2 to
     bf16 — no fp32 θ, no autocast cast) and the fp32 weight-grad path.
     'hand' forces the hand-written kernels everywhere (the A/B switch the
-    probe and profiles use); 'lib' forces the library."""
+    probe and profiles use); 'lib' forces the library.  auto's dgrad is the
+    library's FORWARD conv on the flipped-transposed θ: the library's
+    fastest bwd-data solver on these shapes sums its K-split with atomics,
+    so dx — and every gradient upstream — differed in the last bits from
+    run to run, while its forward solver is as fast and reproducible."""
     return os.environ.get("FLREID_CONV_IMPL", "auto")
 
 
@@ -934,7 +948,7 @@ class _Conv3x3Fn(torch.autograd.Function):
            (gw, atten, aw); conv = hand halo kernel (conv3x3_img*.hip) or
            the library on θ, by policy (_conv_impl).
     dgrad: hand = the same kernel on the flip-transposed θ tile;
-           lib = conv2d_input on θ.
+           auto = conv2d on the flip-transposed θ; lib = conv2d_input on θ.
     wgrad: hand = transpose-first MFMA reduction (fp32 out);
            lib = conv2d_weight (bf16, cast once).  For the adaptive layer
            dθ IS d(adaptive_weight) (identity composition).
@@ -986,8 +1000,12 @@ class _Conv3x3Fn(torch.autograd.Function):
             else:
                 if theta is None:
                     theta = compose_theta_bf16(ext, weight, atten, aw)
-                dx = torch.nn.grad.conv2d_input((n, c, h, w), theta, dy_bf,
-                                                padding=1)
+                if _conv_impl() == "lib":
+                    dx = torch.nn.grad.conv2d_input((n, c, h, w), theta,
+                                                    dy_bf, padding=1)
+                else:
+                    dx = torch.nn.functional.conv2d(
+                        dy_bf, conv_theta_flipt(ext, theta), padding=1)
             if ctx.x_dtype != torch.bfloat16:
                 dx = dx.to(ctx.x_dtype)
         d_weight = d_aw = None

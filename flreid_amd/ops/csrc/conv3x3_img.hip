@@ -104,10 +104,56 @@ __global__ __launch_bounds__(256) void conv3x3_tile_kernel(
   }
 }
 
+// mode 2: the flipped-transposed θ as a PLAIN channels-last conv weight,
+// wT[c][ft][k] = θ[k][flip(ft)][c] (bf16, [C][3][3][K]) — dgrad becomes a
+// forward conv of dy with wT.  Per tap a 32x32 (k, c) tile goes through LDS
+// so both the loads (along c) and the stores (along k) are contiguous.
+template <typename Tin>
+__global__ __launch_bounds__(256) void conv3x3_wt_plain_kernel(
+    const Tin* __restrict__ GW, const float* __restrict__ ATTEN,
+    const Tin* __restrict__ AW, __hip_bfloat16* __restrict__ OUT,
+    int C, int K) {
+  __shared__ float tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+  const int tap = blockIdx.z;
+  const int ft = (2 - tap / 3) * 3 + (2 - tap % 3);
+  const int c0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
+  const float a = ATTEN ? ATTEN[tap % 3] : 1.0f;
+  for (int j = 0; j < 32; j += 8) {
+    const int k = k0 + ty + j, c = c0 + tx;
+    if (k < K && c < C) {
+      const int64_t src = ((int64_t)k * 9 + tap) * C + c;
+      tile[ty + j][tx] = fmaf(a, load_as_float(GW, src),
+                              AW ? load_as_float(AW, src) : 0.0f);
+    }
+  }
+  __syncthreads();
+  for (int j = 0; j < 32; j += 8) {
+    const int c = c0 + ty + j, k = k0 + tx;
+    if (c < C && k < K)
+      OUT[((int64_t)c * 9 + ft) * K + k] = __float2bfloat16(tile[tx][ty + j]);
+  }
+}
+
 extern "C" void flreid_conv3x3_tile(const void* GW, const float* ATTEN,
                                     const void* AW, void* OUT, int C, int K,
                                     int in_dtype, int mode,
                                     hipStream_t stream) {
+  if (mode == 2) {
+    const dim3 grid((C + 31) / 32, (K + 31) / 32, 9);
+    if (in_dtype == kF32) {
+      hipLaunchKernelGGL((conv3x3_wt_plain_kernel<float>), grid, dim3(256), 0,
+                         stream, (const float*)GW, ATTEN, (const float*)AW,
+                         (__hip_bfloat16*)OUT, C, K);
+    } else {
+      hipLaunchKernelGGL((conv3x3_wt_plain_kernel<__hip_bfloat16>), grid,
+                         dim3(256), 0, stream, (const __hip_bfloat16*)GW,
+                         ATTEN, (const __hip_bfloat16*)AW,
+                         (__hip_bfloat16*)OUT, C, K);
+    }
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   const int64_t total = (int64_t)C * 9 * K;
   const int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
   if (in_dtype == kF32) {

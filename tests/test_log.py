@@ -42,7 +42,7 @@ def test_async_ckpt_write_then_read(tmp_path, monkeypatch):
     assert torch.load(p, weights_only=False)["w"].sum() == 4
 
 
-def test_maybe_sync_batches_distributed_gathers():
+def test_maybe_sync_batches_distributed_gathers(tmp_path):
     """maybe_sync gathers only every FLREID_LOG_SYNC_EVERY rounds (and on
     the final round); single-process mode flushes every call."""
     import os
@@ -65,7 +65,7 @@ def test_maybe_sync_batches_distributed_gathers():
 
     os.environ["FLREID_LOG_SYNC_EVERY"] = "5"
     try:
-        log = ExperimentLog("/tmp/flreid_test_log.json")
+        log = ExperimentLog(str(tmp_path / "flreid_test_log.json"))
         ctx = _FakeCtx()
         for r in range(1, 13):
             log.record(f"data.c.{r}.t", {"x": r})

@@ -618,6 +618,42 @@ def test_conv3x3_img_adaptive_fwd_bwd(impl, monkeypatch):
         (aw.grad - aw2.grad).abs().max()
 
 
+def test_conv3x3_auto_dgrad_is_forward_conv_on_flipped_theta(monkeypatch):
+    """auto's dgrad = the library forward conv on wT[c,k,r,s] = θ[k,c,2-r,2-s]
+    (conv3x3_tile mode 2).  Same sums as the library's bwd-data, so per
+    element the two differ by bf16 rounding of one fp32 accumulation each:
+    |Δ| <= 2^-7 |dx| + accumulation-order noise, bounded here by 2^-6 of the
+    tensor's max (a wrong flip or transpose is off by O(max)).  The re-layout
+    itself is exact (checked at a C, K that are no multiples of its 32-wide
+    tile); conv shapes with C != K both ways and the benchmark's layer4
+    shape.  (Whether repeated calls agree bit for bit depends on the solver
+    the library picks, so that is not asserted here.)"""
+    ext = ops._ext_or_raise("conv3x3_tile")
+    torch.manual_seed(4)
+    th = _cl4(torch.randn(40, 24, 3, 3, device="cuda").bfloat16())
+    expect = th.float().flip(2, 3).transpose(0, 1)
+    assert torch.equal(ops.conv_theta_flipt(ext, th).float(), expect)
+
+    for (n, c, h, w, k) in ((2, 32, 16, 8, 64), (3, 96, 8, 4, 32),
+                            (64, 512, 8, 4, 512)):
+        x = _cl4(torch.randn(n, c, h, w, device="cuda").bfloat16())
+        wt = _cl4(torch.randn(k, c, 3, 3, device="cuda") * (1.0 / c))
+        g = _cl4(torch.randn(n, k, h, w, device="cuda").bfloat16())
+
+        def dx_of(impl):
+            monkeypatch.setenv("FLREID_CONV_IMPL", impl)
+            x1 = x.clone().requires_grad_(True)
+            out = ops.conv3x3_try(x1, wt.clone().requires_grad_(True))
+            assert out is not None, (n, c, h, w, k)
+            out.backward(g)
+            return x1.grad.float()
+
+        dx, dx_lib = dx_of("auto"), dx_of("lib")
+        bound = float(dx_lib.abs().max()) * 2 ** -6
+        assert float((dx - dx_lib).abs().max()) <= bound, \
+            (n, c, h, w, k, float((dx - dx_lib).abs().max()), bound)
+
+
 def test_conv3x3_try_regime_guard():
     """Out-of-regime shapes must decline (caller falls back to library)."""
     x = _cl4(torch.randn(2, 64, 32, 16, device="cuda").bfloat16())  # HW=512
