@@ -33,14 +33,65 @@ def bench(fn, n=50, warmup=5):
     return (time.perf_counter() - t0) / n * 1e3
 
 
+def bench_decomposed(results, n):
+    """FedWeIT composition fwd+bwd (decomposed.hip) vs the eager chain:
+    fp32 parameters, bf16 θ, KB=5, at the three layer classes of the
+    benchmark model.  GBps uses the kernels' traffic model: (KB+3) floats
+    per element forward + (KB+4) backward."""
+    kb = 5
+    for tag, shape, cl in (("conv3x3_cl", (512, 512, 3, 3), True),
+                           ("conv1x1", (2048, 512, 1, 1), False),
+                           ("linear", (8000, 2048), False)):
+        sw = torch.randn(shape, device="cuda")
+        aw = torch.randn(shape, device="cuda")
+        go = torch.randn(shape, device="cuda").bfloat16()
+        if cl:
+            sw, aw, go = (t.contiguous(memory_format=torch.channels_last)
+                          for t in (sw, aw, go))
+        aw.requires_grad_(True)
+        mask = torch.rand(shape[0], device="cuda", requires_grad=True)
+        aw_kb = torch.randn(*shape, kb, device="cuda")
+        atten = torch.randn(kb, device="cuda", requires_grad=True)
+
+        def run(compose):
+            theta = compose(sw, mask, aw, aw_kb, atten, 1e-3, 0.0, True)
+            theta.backward(go)
+            aw.grad = mask.grad = atten.grad = None
+
+        def fused(*a):
+            return ops.decomposed_compose(*a, out_dtype=torch.bfloat16)
+
+        def eager(*a):
+            return ref.decomposed_compose(*a).bfloat16()
+
+        results[f"decomposed_{tag}_fused"] = bench(lambda: run(fused), n)
+        results[f"decomposed_{tag}_eager"] = bench(lambda: run(eager), n)
+        nbytes = sw.numel() * 4 * ((kb + 3) + (kb + 4))
+        results[f"decomposed_{tag}_fused_GBps"] = round(
+            nbytes / (results[f"decomposed_{tag}_fused"] / 1e3) / 1e9, 0)
+
+
+def report(results):
+    for k in sorted(results):
+        v = results[k]
+        print(f"{k:28s} {v:10.3f}" + (" ms" if "_TF" not in k and "GBps" not in k else ""))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--once", action="store_true",
                    help="single invocation per op (for PMC counter runs)")
+    p.add_argument("--decomposed-only", action="store_true",
+                   help="run only the FedWeIT composition entry")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
+
+    bench_decomposed(results, n)
+    if args.decomposed_only:
+        report(results)
+        return
 
     # K8: eval similarity GEMM (MFMA f32) — Q×G at validation scale
     qf = ref.l2_normalize(torch.randn(2048, 2048, device="cuda"))
@@ -144,9 +195,7 @@ def main():
     results["drift_fused"] = bench(fused_drift, n)
     results["drift_foreach"] = bench(foreach_drift, n)
 
-    for k in sorted(results):
-        v = results[k]
-        print(f"{k:28s} {v:10.3f}" + (" ms" if "_TF" not in k and "GBps" not in k else ""))
+    report(results)
 
 
 if __name__ == "__main__":

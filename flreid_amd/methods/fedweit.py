@@ -26,6 +26,7 @@ from typing import Any, Dict, List, Optional
 
 import torch
 
+from flreid_amd import ops
 from flreid_amd.methods.common import BaseReIDClient, BaseReIDOperator
 from flreid_amd.models.decomposed import (
     convert_to_decomposed,
@@ -124,10 +125,11 @@ class Model(ModelModule):
         """{name.sw: mask⊙sw + aw + kb·atten} in EVAL composition (no
         pruning), ref:methods/fedweit.py:791-797."""
         out = {}
-        for n, m in self.decomposed_module_leaves():
-            kb = (m.atten * m.aw_kb).sum(dim=-1)
-            out[f"{n}.sw"] = (m.mask.view(m._mask_bcast_shape()) * m.sw
-                              + m.aw + kb).detach().clone()
+        with torch.no_grad():
+            for n, m in self.decomposed_module_leaves():
+                out[f"{n}.sw"] = ops.decomposed_compose(
+                    m.sw, m.mask, m.aw, m.aw_kb, m.atten, m.lambda_l1,
+                    m.lambda_mask, False)
         return out
 
 

@@ -22,10 +22,16 @@ import torch.nn.functional as F
 from torch import nn
 from torch.nn import Parameter
 
+from flreid_amd import ops
+from flreid_amd.ops.reference import l1_hard_threshold  # noqa: F401  (re-export)
 
-def l1_hard_threshold(weights: torch.Tensor, threshold: float) -> torch.Tensor:
-    """w · 1[|w| > λ] (ref:methods/fedweit.py:122-125)."""
-    return weights * torch.greater(weights.abs(), threshold).to(weights.dtype)
+
+def _autocast_dtype(data: torch.Tensor) -> Optional[torch.dtype]:
+    """θ's dtype under CUDA autocast (the composition kernel emits it
+    directly, sparing autocast's fp32→bf16 cast pass); None otherwise."""
+    if data.is_cuda and torch.is_autocast_enabled():
+        return torch.get_autocast_dtype("cuda")
+    return None
 
 
 class DecomposedBase(nn.Module):
@@ -97,16 +103,20 @@ class DecomposedBase(nn.Module):
         self._assign(self.atten, atten.detach())
         self.atten.requires_grad = True
 
-    def composed_weight(self) -> torch.Tensor:
-        aw = self.aw if not self.training else l1_hard_threshold(self.aw, self.lambda_l1)
-        mask = self.mask if not self.training else l1_hard_threshold(self.mask, self.lambda_mask)
-        kb = (self.atten * self.aw_kb).sum(dim=-1)
-        return mask.view(self._mask_bcast_shape()) * self.sw + aw + kb
+    def composed_weight(self, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        """θ (fp32 unless out_dtype says otherwise) — fused HIP
+        forward+backward on GPU, the eager reference chain elsewhere
+        (ops.decomposed_compose)."""
+        return ops.decomposed_compose(self.sw, self.mask, self.aw, self.aw_kb,
+                                      self.atten, self.lambda_l1,
+                                      self.lambda_mask, self.training,
+                                      out_dtype)
 
 
 class DecomposedLinear(DecomposedBase):
     def forward(self, data: torch.Tensor) -> torch.Tensor:
-        return F.linear(data, self.composed_weight(), self.bias)
+        return F.linear(data, self.composed_weight(_autocast_dtype(data)),
+                        self.bias)
 
 
 class DecomposedConv2d(DecomposedBase):
@@ -116,8 +126,8 @@ class DecomposedConv2d(DecomposedBase):
         self.padding = padding
 
     def forward(self, data: torch.Tensor) -> torch.Tensor:
-        return F.conv2d(data, self.composed_weight(), self.bias,
-                        stride=self.stride, padding=self.padding)
+        return F.conv2d(data, self.composed_weight(_autocast_dtype(data)),
+                        self.bias, stride=self.stride, padding=self.padding)
 
 
 class DecomposedBatchNorm2d(DecomposedBase):

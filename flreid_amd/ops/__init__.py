@@ -208,6 +208,122 @@ def adaptive_compose(global_weight: torch.Tensor, atten: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# FedWeIT decomposed-layer composition (decomposed.hip)
+# ---------------------------------------------------------------------------
+
+_TORCH_DT = {torch.float32: _F32, torch.bfloat16: _BF16}
+
+
+def _decomposed_geometry(sw: torch.Tensor):
+    """(rows, C, S, channels_last) of a dense weight, or None.  4-D weights
+    whose two layouts coincide (S == 1 or C == 1) count as contiguous."""
+    rows = sw.shape[0]
+    if sw.dim() == 4:
+        c, s = sw.shape[1], sw.shape[2] * sw.shape[3]
+        if s > 1 and c > 1 and not sw.is_contiguous():
+            if sw.is_contiguous(memory_format=torch.channels_last):
+                return rows, c, s, True
+            return None
+        if sw.is_contiguous() or sw.is_contiguous(
+                memory_format=torch.channels_last):
+            return rows, c, s, False
+        return None
+    if not sw.is_contiguous():
+        return None
+    return rows, sw.numel() // max(rows, 1), 1, False
+
+
+class _DecomposedComposeFn(torch.autograd.Function):
+    """θ = thr(mask)⊙sw + thr(aw) + Σ_k atten_k·aw_kb[..., k] in one kernel
+    per direction.  Only the inputs are saved; the backward re-reads them
+    and emits d_aw, the d_mask partials and the d_atten partials in one
+    pass (the partial sums are finished by torch — deterministic)."""
+
+    @staticmethod
+    def forward(ctx, sw, mask, aw, aw_kb, atten, lambda_l1, lambda_mask,
+                training, out_dtype, geom, ext):
+        rows, c, s, cl = geom
+        kb = aw_kb.shape[-1]
+        out = torch.empty_like(sw, dtype=out_dtype)
+        ext.decomposed_fwd(sw.data_ptr(), mask.data_ptr(), aw.data_ptr(),
+                           aw_kb.data_ptr(), atten.data_ptr(), out.data_ptr(),
+                           rows, c, s, kb, int(cl), int(training),
+                           float(lambda_l1), float(lambda_mask),
+                           _TORCH_DT[out_dtype], _stream())
+        ctx.save_for_backward(sw, mask, aw, aw_kb, atten)
+        ctx.cfg = (geom, float(lambda_l1), float(lambda_mask), bool(training),
+                   out_dtype, ext)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        sw, mask, aw, aw_kb, atten = ctx.saved_tensors
+        (rows, c, s, cl), l1, lm, training, out_dtype, ext = ctx.cfg
+        need_mask, need_aw, need_atten = (ctx.needs_input_grad[1],
+                                          ctx.needs_input_grad[2],
+                                          ctx.needs_input_grad[4])
+        if not (need_mask or need_aw or need_atten):
+            return (None,) * 11
+        kb = aw_kb.shape[-1]
+        # dθ in θ's dtype and layout
+        g = grad_out.to(out_dtype)
+        g = g.contiguous(memory_format=torch.channels_last) if cl \
+            else g.contiguous()
+        tpr, blocks = ext.decomposed_plan(rows, c, s, int(cl))
+        dev = sw.device
+        d_aw = torch.empty_like(aw) if need_aw else None
+        dm_part = (torch.empty(rows, tpr, device=dev, dtype=torch.float32)
+                   if need_mask else None)
+        da_part = (torch.empty(blocks, kb, device=dev, dtype=torch.float32)
+                   if need_atten else None)
+        ext.decomposed_bwd(
+            g.data_ptr(), _TORCH_DT[out_dtype], sw.data_ptr(),
+            mask.data_ptr(), aw.data_ptr(), aw_kb.data_ptr(),
+            d_aw.data_ptr() if need_aw else 0,
+            dm_part.data_ptr() if need_mask else 0,
+            da_part.data_ptr() if need_atten else 0,
+            rows, c, s, kb, int(cl), int(training), l1, lm,
+            int(need_aw), int(need_mask), int(need_atten), _stream())
+        d_mask = dm_part.sum(dim=1).view(mask.shape) if need_mask else None
+        d_atten = da_part.sum(dim=0).view(atten.shape) if need_atten else None
+        return (None, d_mask, d_aw, None, d_atten) + (None,) * 6
+
+
+def decomposed_compose(sw: torch.Tensor, mask: torch.Tensor, aw: torch.Tensor,
+                       aw_kb: torch.Tensor, atten: torch.Tensor,
+                       lambda_l1: float, lambda_mask: float, training: bool,
+                       out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """FedWeIT composed weight.  Fused HIP forward+backward on GPU for fp32
+    dense weights of dim ≥ 2 (contiguous, or channels-last for 4-D) with a
+    frozen sw; the eager reference everywhere else (1-D BN/LN weights, CPU,
+    mismatched layouts).  out_dtype (fp32 default, or bf16) is θ's dtype:
+    bf16 is the round-to-nearest-even cast of the fp32 θ, emitted by the
+    kernel directly.  FLREID_NO_FUSED_DECOMPOSE=1 forces the reference."""
+    if (sw.is_cuda and os.environ.get("FLREID_NO_FUSED_DECOMPOSE", "0") != "1"
+            and out_dtype in (None, torch.float32, torch.bfloat16)
+            and all(t.is_cuda and t.dtype == torch.float32
+                    for t in (sw, mask, aw, aw_kb, atten))
+            and sw.dim() >= 2 and sw.numel() > 0 and not sw.requires_grad
+            and not aw_kb.requires_grad and aw.shape == sw.shape
+            and aw_kb.dim() == sw.dim() + 1 and aw_kb.shape[:-1] == sw.shape
+            and aw_kb.shape[-1] >= 1 and aw_kb.is_contiguous()
+            and atten.numel() == aw_kb.shape[-1] and atten.is_contiguous()
+            and mask.numel() == sw.shape[0] and mask.is_contiguous()):
+        geom = _decomposed_geometry(sw)
+        if geom is not None and geom == _decomposed_geometry(aw):
+            ext = _ext_or_raise("decomposed_fwd")
+            if ext is not None:
+                return _DecomposedComposeFn.apply(
+                    sw, mask, aw, aw_kb, atten, lambda_l1, lambda_mask,
+                    bool(training), out_dtype or torch.float32, geom, ext)
+    out = ref.decomposed_compose(sw, mask, aw, aw_kb, atten, lambda_l1,
+                                 lambda_mask, training)
+    if out_dtype is not None and out.dtype != out_dtype:
+        out = out.to(out_dtype)
+    return out
+
+
+# ---------------------------------------------------------------------------
 # EWC/MAS importance accumulation (K9)
 # ---------------------------------------------------------------------------
 

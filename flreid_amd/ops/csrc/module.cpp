@@ -92,6 +92,19 @@ extern "C" void flreid_drift_fwd(const int64_t*, const int*, float*, int,
                                  hipStream_t);
 extern "C" void flreid_drift_bwd(const int64_t*, const int*, const float*,
                                  float*, int, hipStream_t);
+extern "C" void flreid_decomposed_plan(int64_t, int64_t, int64_t, int,
+                                       int64_t*, int64_t*);
+extern "C" void flreid_decomposed_fwd(const float*, const float*,
+                                      const float*, const float*,
+                                      const float*, void*, int64_t, int64_t,
+                                      int64_t, int64_t, int, int, float,
+                                      float, int, hipStream_t);
+extern "C" void flreid_decomposed_bwd(const void*, int, const float*,
+                                      const float*, const float*,
+                                      const float*, float*, float*, float*,
+                                      int64_t, int64_t, int64_t, int64_t, int,
+                                      int, float, float, int, int, int,
+                                      hipStream_t);
 }  // namespace flreid
 
 namespace py = pybind11;
@@ -355,5 +368,42 @@ PYBIND11_MODULE(_flreid_hip, m) {
                                      (const int*)p_idx, (const int*)n_idx,
                                      (float*)grad, N, D, coeff,
                                      as_stream(stream));
+        });
+
+  // (tasks_per_row, blocks): dmask_part is [rows][tasks_per_row],
+  // datten_part is [blocks][KB]
+  m.def("decomposed_plan",
+        [](int64_t rows, int64_t C, int64_t S, int channels_last) {
+          int64_t tpr = 0, blocks = 0;
+          flreid::flreid_decomposed_plan(rows, C, S, channels_last, &tpr,
+                                         &blocks);
+          return py::make_tuple(tpr, blocks);
+        });
+
+  m.def("decomposed_fwd",
+        [](uintptr_t sw, uintptr_t mask, uintptr_t aw, uintptr_t aw_kb,
+           uintptr_t atten, uintptr_t out, int64_t rows, int64_t C, int64_t S,
+           int64_t KB, int channels_last, int train, float lambda_l1,
+           float lambda_mask, int out_dtype, uintptr_t stream) {
+          flreid::flreid_decomposed_fwd(
+              (const float*)sw, (const float*)mask, (const float*)aw,
+              (const float*)aw_kb, (const float*)atten, (void*)out, rows, C,
+              S, KB, channels_last, train, lambda_l1, lambda_mask, out_dtype,
+              as_stream(stream));
+        });
+
+  m.def("decomposed_bwd",
+        [](uintptr_t g, int g_dtype, uintptr_t sw, uintptr_t mask,
+           uintptr_t aw, uintptr_t aw_kb, uintptr_t d_aw,
+           uintptr_t dmask_part, uintptr_t datten_part, int64_t rows,
+           int64_t C, int64_t S, int64_t KB, int channels_last, int train,
+           float lambda_l1, float lambda_mask, int need_aw, int need_mask,
+           int need_atten, uintptr_t stream) {
+          flreid::flreid_decomposed_bwd(
+              (const void*)g, g_dtype, (const float*)sw, (const float*)mask,
+              (const float*)aw, (const float*)aw_kb, (float*)d_aw,
+              (float*)dmask_part, (float*)datten_part, rows, C, S, KB,
+              channels_last, train, lambda_l1, lambda_mask, need_aw,
+              need_mask, need_atten, as_stream(stream));
         });
 }

@@ -224,6 +224,29 @@ def adaptive_compose(global_weight: torch.Tensor, atten: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# FedWeIT decomposed-layer composition (ref:methods/fedweit.py:122-136)
+# ---------------------------------------------------------------------------
+
+def l1_hard_threshold(weights: torch.Tensor, threshold: float) -> torch.Tensor:
+    """w · 1[|w| > λ] (ref:methods/fedweit.py:122-125)."""
+    return weights * torch.greater(weights.abs(), threshold).to(weights.dtype)
+
+
+def decomposed_compose(sw: torch.Tensor, mask: torch.Tensor, aw: torch.Tensor,
+                       aw_kb: torch.Tensor, atten: torch.Tensor,
+                       lambda_l1: float, lambda_mask: float,
+                       training: bool) -> torch.Tensor:
+    """θ = mask ⊙ sw + aw + Σ_k atten_k · aw_kb[..., k]; mask is
+    per-output-channel (broadcast over all dims but dim 0); aw and mask are
+    L1-hard-thresholded when training."""
+    if training:
+        aw = l1_hard_threshold(aw, lambda_l1)
+        mask = l1_hard_threshold(mask, lambda_mask)
+    kb = (atten * aw_kb).sum(dim=-1)
+    return mask.view((-1,) + (1,) * (sw.dim() - 1)) * sw + aw + kb
+
+
+# ---------------------------------------------------------------------------
 # CMC / mAP evaluation (ref:tools/evaluate.py)
 # ---------------------------------------------------------------------------
 
