@@ -1137,6 +1137,12 @@ class _Conv3x3Fn(torch.autograd.Function):
                                   dtype=torch.bfloat16)
                 xt = torch.empty(c * m_rows + 256, device=dy.device,
                                  dtype=torch.bfloat16)
+                if m_rows % 64:
+                    # xT is masked per element, dyT only per row: the last
+                    # chunk of dyT's row K-1 multiplies its tail pad by the
+                    # zeroed xT lanes, and 0·NaN = NaN — so the pad must be
+                    # finite.  Aligned M never reads it.
+                    dyt[-128:].zero_()
                 ext.transpose_bf16(dy_bf.data_ptr(), dyt.data_ptr() + 256,
                                    m_rows, k, _stream())
                 ext.transpose_bf16(x_bf.data_ptr(), xt.data_ptr() + 256,

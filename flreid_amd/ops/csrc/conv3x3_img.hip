@@ -449,8 +449,11 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(
 
   // DYT/XT carry ≥128-elem pads on both ends (the wrapper allocates them),
   // so shifted/tail chunk addresses are loaded UNCLAMPED — a clamp would
-  // misalign the chunk's element<->m correspondence.  Out-of-range lanes
-  // read pad/neighbour-row bytes and are zero-masked at the LDS store.
+  // misalign the chunk's element<->m correspondence.  Out-of-range XT
+  // lanes read pad/neighbour-row bytes and are zero-masked at the LDS
+  // store.  DYT is masked per ROW only: its m >= M lanes (last chunk when
+  // M % 64 != 0) meet zeroed XT lanes, so they need only be FINITE — the
+  // next row's data is; for row K-1 the caller zeroes DYT's tail pad.
   auto load_tile = [&](int64_t m0) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
