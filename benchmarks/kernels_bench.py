@@ -71,6 +71,80 @@ def bench_decomposed(results, n):
             nbytes / (results[f"decomposed_{tag}_fused"] / 1e3) / 1e9, 0)
 
 
+def bench_head_step(results, n):
+    """One-pass FedSTIL head update (head_step.hip) over the ResNet-50
+    head's 11 adaptive weights (31.3 M fp32: layer4 channels-last convs +
+    the 8000×2048 classifier) against the chain it replaces — drift
+    fwd+bwd, gradient cast + add, torch's fused Adam, compose2 — and the
+    classifier forward on a ready bf16 θ: K2 tile loop with the bf16-load
+    prologue vs the composing K2 kernel vs a plain bf16 GEMM.  GBps uses the
+    36 B/element model (read aw, aw0, bf16 dw, gw, m, v; write aw, m, v and
+    bf16 θ)."""
+    shapes = [(512, 1024, 1, 1), (512, 512, 3, 3), (2048, 512, 1, 1),
+              (2048, 1024, 1, 1)]
+    shapes += [(512, 2048, 1, 1), (512, 512, 3, 3), (2048, 512, 1, 1)] * 2
+    shapes += [(8000, 2048)]
+
+    def mk(shape, dtype=torch.float32, scale=0.05):
+        t = torch.randn(shape, device="cuda") * scale
+        if len(shape) == 4:
+            t = t.contiguous(memory_format=torch.channels_last)
+        return t.to(dtype)
+
+    rows, params, anchors, gws, attens, dws = [], [], [], [], [], []
+    for shp in shapes:
+        aw0 = mk(shp)
+        aw = aw0 + mk(shp, scale=1e-3)
+        row = {"aw": aw.clone(), "aw0": aw0, "dw": mk(shp, torch.bfloat16, 1e-2),
+               "gw": mk(shp), "atten": torch.full((shp[-1],), 0.9, device="cuda"),
+               "m": torch.zeros_like(aw), "v": torch.zeros_like(aw),
+               "step": torch.zeros((), device="cuda"),
+               "theta": torch.empty_like(aw, dtype=torch.bfloat16)}
+        rows.append(row)
+        params.append(torch.nn.Parameter(aw.clone()))
+        anchors.append(aw0)
+        gws.append(row["gw"]); attens.append(row["atten"]); dws.append(row["dw"])
+    numel = sum(r["aw"].numel() for r in rows)
+    partials = torch.zeros(ops.head_step_partials(rows), dtype=torch.float64,
+                           device="cuda")
+    hyper = (1e-3, 0.9, 0.999, 1e-5, 1e-8, 1e-4)
+
+    def fused():
+        ops.head_step(rows, partials, *hyper)
+        return partials.sum()
+
+    opt = torch.optim.Adam(params, lr=1e-3, weight_decay=1e-5, fused=True,
+                           capturable=True)
+    ext = ops._ext_or_raise("compose2")
+    pairs = list(zip(params, anchors))
+
+    def unfused():
+        loss = ops.l1_drift(pairs) * 1e-4
+        loss.backward()
+        for p, dw in zip(params, dws):
+            p.grad += dw.to(torch.float32)
+        opt.step()
+        for p, gw, at in zip(params, gws, attens):
+            ops.compose_theta_bf16(ext, gw, at, p.detach())
+            p.grad = None
+
+    results["head_step_fused"] = bench(fused, n)
+    results["head_step_unfused_chain"] = bench(unfused, n)
+    results["head_step_fused_GBps"] = round(
+        numel * 36 / (results["head_step_fused"] / 1e3) / 1e9, 0)
+
+    x = (torch.randn(64, 2048, device="cuda") * 0.5).bfloat16()
+    cls = rows[-1]
+    with torch.no_grad():
+        results["classifier_fwd_k2_theta"] = bench(
+            lambda: ops.theta_linear(x, cls["theta"], None, k2=True), n)
+        results["classifier_fwd_k2_compose"] = bench(
+            lambda: ops.adaptive_linear_fwd(x, cls["gw"], cls["atten"],
+                                            cls["aw"], None), n)
+        results["classifier_fwd_bf16_gemm"] = bench(
+            lambda: x @ cls["theta"].t(), n)
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
@@ -83,11 +157,18 @@ def main():
                    help="single invocation per op (for PMC counter runs)")
     p.add_argument("--decomposed-only", action="store_true",
                    help="run only the FedWeIT composition entry")
+    p.add_argument("--head-step-only", action="store_true",
+                   help="run only the FedSTIL one-pass head update entry")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
 
+    if args.head_step_only:
+        bench_head_step(results, n)
+        report(results)
+        return
+    bench_head_step(results, n)
     bench_decomposed(results, n)
     if args.decomposed_only:
         report(results)

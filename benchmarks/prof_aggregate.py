@@ -43,7 +43,10 @@ def main(db_glob: str, top: int = 40, tail_frac: float = 0.0):
         print(f"{'kernel':<72s} {'calls':>7s} {'total_ms':>9s} "
               f"{'avg_us':>8s} {'%':>5s}")
         for name, (n, us) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:top]:
-            short = name.split("(")[0][:72]
+            # "(anonymous namespace)::" would cut torch's multi-tensor
+            # kernels down to "void at::native::"
+            short = name.replace("(anonymous namespace)::", "")
+            short = short.split("(")[0][:72]
             print(f"{short:<72s} {n:>7d} {us/1e3:>9.2f} {us/n:>8.1f} "
                   f"{100*us/total:>5.1f}")
 

@@ -31,6 +31,7 @@ personalized mixtures are local, deterministic computations.
 
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Any, Dict, List, Optional
 
@@ -38,7 +39,11 @@ import torch
 from torch.utils.data import DataLoader
 
 from flreid_amd import ops
-from flreid_amd.methods.common import BaseReIDClient, BaseReIDOperator
+from flreid_amd.methods.common import (
+    BaseReIDClient,
+    BaseReIDOperator,
+    FusedHeadStep,
+)
 from flreid_amd.models.adaptive import (
     adaptive_leaves,
     convert_to_adaptive,
@@ -408,6 +413,21 @@ class TensorBatches:
                    self.classes.index_select(0, idx_cpu))
 
 
+@contextlib.contextmanager
+def head_epoch(model, operator, capturable: bool = True):
+    """Scope of one head-training epoch: rebinds the optimizer, decides —
+    once, for the whole model — whether the steps take the one-pass head
+    update (FusedHeadStep, None when ineligible) and keeps the live bf16 θ
+    attached to the adaptive leaves until the epoch ends, exceptions
+    included.  `operator._train_step` is the step body inside it."""
+    operator.set_optimizer_parameters(model, capturable=capturable)
+    plan = FusedHeadStep.plan(model, operator.optimizer, model.device,
+                              previous=getattr(operator, "_fused_head", None))
+    operator._fused_head = plan
+    with plan.live_theta() if plan is not None else contextlib.nullcontext():
+        yield plan
+
+
 class Operator(BaseReIDOperator):
     def generate_proto_loader(self, model: Model, source_loader: DataLoader):
         """Prototype capture pass (ref:methods/fedstil.py:558-617): one frozen
@@ -493,6 +513,11 @@ class Operator(BaseReIDOperator):
         """One head-training step — eager body AND the hipGraph-captured fn
         (must stay replay-safe: fixed shapes, no host syncs)."""
         device = model.device
+        # one-pass head update (decided per epoch in invoke_train): the L1
+        # drift leaves autograd, the task loss back-propagates alone and
+        # FusedHeadStep adds the sign term, applies Adam to the adaptive
+        # weights and hands back the drift value
+        fused = getattr(self, "_fused_head", None)
         # set_to_none also under graph capture: backward's AccumulateGrad
         # allocates each .grad from the capture pool exactly once, so replays
         # rewrite the same buffers — and the ~70 fill/accumulate launches per
@@ -503,11 +528,17 @@ class Operator(BaseReIDOperator):
             loss = 0.0
             for loss_func in self.criterion:
                 loss = loss + loss_func(score=score, feature=feature, target=target)
-            loss = loss + model.drift_loss() * model.lambda_l1
+            if fused is None:
+                loss = loss + model.drift_loss() * model.lambda_l1
         loss.backward()
+        if fused is not None:
+            fused.step(model.lambda_l1)
         self.optimizer.step()
+        loss = loss.detach()
+        if fused is not None:
+            loss = loss + fused.drift() * model.lambda_l1
         b_acc = (score.detach().argmax(dim=1) == target).sum()
-        return loss.detach(), b_acc
+        return loss, b_acc
 
     def _graphed_step(self, model: Model, batch_size: int):
         """Per-(operator, batch-size, lr) cached GraphedStep; recaptured when
@@ -519,7 +550,9 @@ class Operator(BaseReIDOperator):
         # which invalidates captured pointers
         shapes = tuple(tuple(p.shape) for p in
                        self.optimizer.param_groups[0]["params"])
-        key = (batch_size, float(lr), shapes)
+        # a graph bakes which update path it captured (and its buffers)
+        key = (batch_size, float(lr), shapes,
+               id(getattr(self, "_fused_head", None)))
         cache = getattr(self, "_train_graphs", None)
         if cache is None or cache[0] != key:
             gs = GraphedStep(lambda d, t: self._train_step(model, d, t))
@@ -534,7 +567,8 @@ class Operator(BaseReIDOperator):
         lr = float(self.optimizer.param_groups[0]["lr"])
         shapes = tuple(tuple(p.shape) for p in
                        self.optimizer.param_groups[0]["params"])
-        key = (tuple(loader.data.shape), batch, steps, lr, shapes)
+        key = (tuple(loader.data.shape), batch, steps, lr, shapes,
+               id(getattr(self, "_fused_head", None)))
         cache = getattr(self, "_epoch_graph_cache", None)
         if cache is None or cache[0] != key:
             eg = EpochGraph(lambda d, t: self._train_step(model, d, t),
@@ -555,65 +589,67 @@ class Operator(BaseReIDOperator):
             proto_loader, task_token = self.generate_proto_loader(model, dataloader)
 
         model.train()
-        self.set_optimizer_parameters(model, capturable=use_graph)
         batch_size = getattr(proto_loader, "batch_size", None)
-        _phase_head = phase("head_epoch"); _phase_head.__enter__()
+        with contextlib.ExitStack() as scope:
+            scope.enter_context(phase("head_epoch"))
+            # optimizer rebind + fused-update eligibility + live θ, for
+            # exactly this epoch
+            scope.enter_context(head_epoch(model, self, capturable=use_graph))
 
-        use_epoch = (use_graph and epoch_graph_enabled()
-                     and isinstance(proto_loader, TensorBatches)
-                     and proto_loader.data.is_cuda
-                     and proto_loader._pids_dev is not None
-                     and proto_loader.data.shape[0] >= batch_size)
-        if use_epoch:
-            # the whole rehearsal epoch as one graph replay: S in-graph
-            # steps + an eager tail, preserving TensorBatches' shuffle and
-            # drop_last semantics (one host sync per epoch for the metrics)
-            n = proto_loader.data.shape[0]
-            steps = n // batch_size
-            order = torch.randperm(n)
-            eg = self._epoch_graph(model, proto_loader)
-            idx_flat = order[:steps * batch_size].to(device, non_blocking=True)
-            loss_dev, acc_dev = eg.run(proto_loader.data,
-                                       proto_loader._pids_dev, idx_flat)
-            batch_cnt, data_cnt = steps, steps * batch_size
-            stop = (steps * batch_size
-                    if (proto_loader.drop_last or n % batch_size == 0) else n)
-            if stop > steps * batch_size:
-                tail = order[steps * batch_size:stop].to(device)
-                d = proto_loader.present(
-                    proto_loader.data.index_select(0, tail))
-                t = proto_loader._pids_dev.index_select(0, tail)
-                b_loss, b_acc = self._train_step(model, d, t)
-                loss_dev = loss_dev + b_loss
-                acc_dev = acc_dev + b_acc
-                batch_cnt += 1
-                data_cnt += tail.numel()
-        else:
-            gs = self._graphed_step(model, batch_size) if use_graph else None
-            warmups = 0
+            use_epoch = (use_graph and epoch_graph_enabled()
+                         and isinstance(proto_loader, TensorBatches)
+                         and proto_loader.data.is_cuda
+                         and proto_loader._pids_dev is not None
+                         and proto_loader.data.shape[0] >= batch_size)
+            if use_epoch:
+                # the whole rehearsal epoch as one graph replay: S in-graph
+                # steps + an eager tail, preserving TensorBatches' shuffle and
+                # drop_last semantics (one host sync per epoch for the metrics)
+                n = proto_loader.data.shape[0]
+                steps = n // batch_size
+                order = torch.randperm(n)
+                eg = self._epoch_graph(model, proto_loader)
+                idx_flat = order[:steps * batch_size].to(device, non_blocking=True)
+                loss_dev, acc_dev = eg.run(proto_loader.data,
+                                           proto_loader._pids_dev, idx_flat)
+                batch_cnt, data_cnt = steps, steps * batch_size
+                stop = (steps * batch_size
+                        if (proto_loader.drop_last or n % batch_size == 0) else n)
+                if stop > steps * batch_size:
+                    tail = order[steps * batch_size:stop].to(device)
+                    d = proto_loader.present(
+                        proto_loader.data.index_select(0, tail))
+                    t = proto_loader._pids_dev.index_select(0, tail)
+                    b_loss, b_acc = self._train_step(model, d, t)
+                    loss_dev = loss_dev + b_loss
+                    acc_dev = acc_dev + b_acc
+                    batch_cnt += 1
+                    data_cnt += tail.numel()
+            else:
+                gs = self._graphed_step(model, batch_size) if use_graph else None
+                warmups = 0
 
-            # device-side metric accumulators; always out-of-place adds so
-            # replay outputs (static tensors) are consumed before the next
-            # replay
-            acc_dev = loss_dev = None
-            for data, person_id, _class_id in proto_loader:
-                data = data.to(device, non_blocking=True)
-                target = person_id.to(device, non_blocking=True)
-                if gs is not None and data.shape[0] == batch_size:
-                    if gs.ready:
-                        b_loss, b_acc = gs(data, target)
-                    elif warmups < 2:
-                        b_loss, b_acc = gs.warmup(data, target)
-                        warmups += 1
+                # device-side metric accumulators; always out-of-place adds so
+                # replay outputs (static tensors) are consumed before the next
+                # replay
+                acc_dev = loss_dev = None
+                for data, person_id, _class_id in proto_loader:
+                    data = data.to(device, non_blocking=True)
+                    target = person_id.to(device, non_blocking=True)
+                    if gs is not None and data.shape[0] == batch_size:
+                        if gs.ready:
+                            b_loss, b_acc = gs(data, target)
+                        elif warmups < 2:
+                            b_loss, b_acc = gs.warmup(data, target)
+                            warmups += 1
+                        else:
+                            b_loss, b_acc = gs.capture(data, target)
                     else:
-                        b_loss, b_acc = gs.capture(data, target)
-                else:
-                    b_loss, b_acc = self._train_step(model, data, target)
-                acc_dev = b_acc.clone() if acc_dev is None else acc_dev + b_acc
-                loss_dev = b_loss.clone() if loss_dev is None else loss_dev + b_loss
-                data_cnt += len(data)
-                batch_cnt += 1
-        _phase_head.__exit__(None, None, None)
+                        b_loss, b_acc = self._train_step(model, data, target)
+                    acc_dev = b_acc.clone() if acc_dev is None else acc_dev + b_acc
+                    loss_dev = b_loss.clone() if loss_dev is None else loss_dev + b_loss
+                    data_cnt += len(data)
+                    batch_cnt += 1
         if acc_dev is not None:       # single host sync per epoch
             train_acc = float(acc_dev)
             train_loss = float(loss_dev)

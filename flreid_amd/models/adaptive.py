@@ -22,6 +22,7 @@ dims but the last.
 
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Optional, Tuple
 
@@ -33,8 +34,72 @@ from torch.nn import Parameter
 from flreid_amd import ops
 
 
+def live_theta_enabled() -> bool:
+    return os.environ.get("FLREID_LIVE_THETA", "1") != "0"
+
+
+class _LiveThetaFn(torch.autograd.Function):
+    """adaptive_weight → the leaf's live bf16 θ.  Forward hands out the
+    buffer; backward stashes the incoming bf16 dθ for the head_step kernel
+    (dθ IS d(adaptive_weight): identity composition) and returns no
+    gradient, so adaptive_weight.grad stays None."""
+
+    @staticmethod
+    def forward(ctx, aw, live):
+        ctx.live = live
+        return live.theta.detach()
+
+    @staticmethod
+    def backward(ctx, g):
+        live = ctx.live
+        if g.dtype != torch.bfloat16:
+            g = g.to(torch.bfloat16)
+        if not ops._same_layout(g, live.theta):
+            # e.g. an NCHW-ordered conv2d_weight result for a channels-last θ
+            g = torch.empty_like(live.theta).copy_(g)
+        live.grad = g if live.grad is None else live.grad + g
+        return None, None
+
+
+class LiveTheta:
+    """θ = atten ⊙ gw + aw of one adaptive leaf in bf16, alive for exactly
+    one head epoch (live_theta_scope): composed at epoch start, kept current
+    by the head_step kernel after every update, dropped at epoch end.
+    Every consumer (F.conv2d, F.linear, the 3×3 and 1×1 routes, the
+    classifier GEMM) sees an ordinary bf16 weight; `grad` is the bf16 dθ the
+    last backward left for the kernel."""
+
+    def __init__(self, theta: torch.Tensor):
+        self.theta = theta
+        self.grad: Optional[torch.Tensor] = None
+
+    def __call__(self, adaptive_weight: torch.Tensor) -> torch.Tensor:
+        return _LiveThetaFn.apply(adaptive_weight, self)
+
+
+@contextlib.contextmanager
+def live_theta_scope(leaves, buffers):
+    """Attach a freshly composed live θ to every leaf for the length of one
+    head epoch; detached on exit, exceptions included.  Nothing outside the
+    scope ever reads the buffers (herding, validation, uploads and dispatch
+    re-inits go through composed_weight), so a stale θ cannot be observed."""
+    ext = ops._ext_or_raise("compose2")
+    try:
+        for leaf, buf in zip(leaves, buffers):
+            ops.compose_theta_bf16(ext, leaf.global_weight,
+                                   leaf.global_weight_atten,
+                                   leaf.adaptive_weight, out=buf)
+            leaf._live = LiveTheta(buf)
+        yield
+    finally:
+        for leaf in leaves:
+            leaf._live = None
+
+
 class AdaptiveBase(nn.Module):
     """Holds the decomposed parameter set; subclasses implement forward."""
+
+    _live: Optional[LiveTheta] = None     # set only inside live_theta_scope
 
     def __init__(self, global_weight: torch.Tensor,
                  global_weight_atten: Optional[torch.Tensor] = None,
@@ -103,6 +168,19 @@ class AdaptiveBase(nn.Module):
 
 class AdaptiveLinear(AdaptiveBase):
     def forward(self, data: torch.Tensor) -> torch.Tensor:
+        if self._live is not None:
+            # head epoch: θ is read from the live buffer, not composed
+            theta = self._live(self.adaptive_weight)
+            # forward GEMM: the K2 tile loop on the ready θ by default — it
+            # sums in the composing K2 kernel's order, so the round stays
+            # bit-identical to the unfused path.  FLREID_CLASSIFIER_GEMM=lib
+            # takes hipBLASLt instead (faster at 64×8000×2048, other
+            # summation order — profiles/README.md)
+            k2 = os.environ.get("FLREID_CLASSIFIER_GEMM", "k2") != "lib"
+            y = ops.theta_linear(data, theta, self.adaptive_bias, k2=k2) \
+                if data.dim() == 2 else None
+            return y if y is not None else F.linear(data, theta,
+                                                    self.adaptive_bias)
         if data.dim() == 2:
             # fused MFMA GEMM with compose-in-prologue (K2); falls back to
             # compose + F.linear off-GPU or when atten trains
@@ -127,7 +205,30 @@ class AdaptiveConv2d(AdaptiveBase):
         self.stride = stride
         self.padding = padding
 
+    def _forward_live(self, data: torch.Tensor) -> torch.Tensor:
+        """Head-epoch forward on the live bf16 θ — the routes of forward()
+        without their compose and gradient-cast passes."""
+        theta = self._live(self.adaptive_weight)
+        k = theta.shape
+        if (k[2] == 3 and k[3] == 3 and _is_one(self.stride)
+                and _is_one(self.padding) and self.adaptive_bias is None):
+            y = ops.conv3x3_try(data, theta)
+            if y is not None:
+                return y
+        if (k[2] == 1 and k[3] == 1 and _is_one(self.stride)
+                and _is_zero(self.padding)
+                and os.environ.get("FLREID_NO_FUSED_1X1", "0") != "1"):
+            b, c, h, w = data.shape
+            xv = data.permute(0, 2, 3, 1).reshape(-1, c)
+            y = ops.theta_linear(xv, theta.view(k[0], c), self.adaptive_bias)
+            if y is not None:
+                return y.view(b, h, w, -1).permute(0, 3, 1, 2)
+        return F.conv2d(data, theta, self.adaptive_bias,
+                        stride=self.stride, padding=self.padding)
+
     def forward(self, data: torch.Tensor) -> torch.Tensor:
+        if self._live is not None and self.global_weight.dim() == 4:
+            return self._forward_live(data)
         gw = self.global_weight
         if (data.is_cuda and gw.dim() == 4 and gw.shape[2] == 3
                 and gw.shape[3] == 3 and _is_one(self.stride)

@@ -940,14 +940,18 @@ def _cl(t: torch.Tensor) -> torch.Tensor:
 
 
 def compose_theta_bf16(ext, gw: torch.Tensor, atten: Optional[torch.Tensor],
-                       aw: Optional[torch.Tensor]) -> torch.Tensor:
+                       aw: Optional[torch.Tensor],
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """θ = atten⊙gw + aw composed DIRECTLY to bf16 in the weight's own
     physical layout (compose2 kernel) — one pass, no fp32 θ in HBM, no
     autocast cast kernel.  atten broadcasts over the LOGICAL last dim; for
     channels-last 4-D weights the physical index of that dim is
-    (i / C) % kw."""
+    (i / C) % kw.  `out`: a bf16 buffer in gw's layout to compose into."""
     gw_d = gw.detach()
-    if gw_d.dim() == 4:
+    if gw_d.dim() == 4 and gw_d.is_contiguous():
+        # NCHW-ordered 4-D weight: the last dim is physically last too
+        inner, L = 1, gw_d.shape[-1]
+    elif gw_d.dim() == 4:
         assert gw_d.is_contiguous(memory_format=torch.channels_last)
         inner, L = gw_d.shape[1], gw_d.shape[-1]
     else:
@@ -956,7 +960,10 @@ def compose_theta_bf16(ext, gw: torch.Tensor, atten: Optional[torch.Tensor],
         L = atten.numel() if atten is not None else 1
     if atten is not None:
         assert atten.numel() == L
-    out = torch.empty_like(gw_d, dtype=torch.bfloat16)
+    if out is None:
+        out = torch.empty_like(gw_d, dtype=torch.bfloat16)
+    elif out.dtype != torch.bfloat16 or not _same_layout(out, gw_d):
+        raise ValueError("compose_theta_bf16: out must be bf16 in gw's layout")
     ext.compose2(gw_d.data_ptr(),
                  atten.detach().float().contiguous().data_ptr() if atten is not None else 0,
                  aw.detach().data_ptr() if aw is not None else 0,
@@ -992,6 +999,61 @@ class _AdaptiveLinear1x1Fn(torch.autograd.Function):
         d_aw = (g.t() @ x_bf).to(torch.float32)
         d_bias = grad_out.sum(0).to(torch.float32) if ctx.has_bias else None
         return dx, None, None, d_aw, d_bias
+
+
+class _ThetaLinearFn(torch.autograd.Function):
+    """y = x·θᵀ + bias on a ready bf16 θ (the head epoch's live θ): the same
+    GEMMs as _AdaptiveLinearFn / _AdaptiveLinear1x1Fn without their compose
+    and cast passes — θ is read as it is and its gradient leaves in bf16.
+    k2: forward on the K2 tile loop with the bf16-load prologue
+    (bit-identical to the composing K2 kernel); else hipBLASLt."""
+
+    @staticmethod
+    def forward(ctx, x, theta, bias, k2):
+        x_bf = x.detach().to(torch.bfloat16).contiguous()
+        th = theta.detach()
+        if k2:
+            ext = _ext_or_raise("theta_linear_fwd")
+            m, k = x_bf.shape
+            n = th.shape[0]
+            y = torch.empty(m, n, device=x.device, dtype=torch.bfloat16)
+            ext.theta_linear_fwd(
+                x_bf.data_ptr(), th.data_ptr(),
+                bias.detach().contiguous().float().data_ptr()
+                if bias is not None else 0,
+                y.data_ptr(), m, n, k, _stream())
+        else:
+            y = x_bf @ th.t()
+            if bias is not None:
+                y = y + bias.detach().to(torch.bfloat16)
+        ctx.save_for_backward(x_bf, th)
+        ctx.x_dtype = x.dtype
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x_bf, th = ctx.saved_tensors
+        g = grad_out.to(torch.bfloat16)
+        dx = (g @ th).to(ctx.x_dtype) if ctx.needs_input_grad[0] else None
+        d_theta = g.t() @ x_bf
+        d_bias = grad_out.sum(0).to(torch.float32) if ctx.has_bias else None
+        return dx, d_theta, d_bias, None
+
+
+def theta_linear(x2d: torch.Tensor, theta2d: torch.Tensor,
+                 bias: Optional[torch.Tensor],
+                 k2: bool = False) -> Optional[torch.Tensor]:
+    """Linear layer on a ready bf16 θ [N, K]; None when out of regime (the
+    caller runs F.linear on θ)."""
+    if (not x2d.is_cuda or x2d.dim() != 2 or not extension_available()
+            or theta2d.dtype != torch.bfloat16
+            or not theta2d.is_contiguous()):
+        return None
+    if x2d.dtype != torch.bfloat16 and not torch.is_autocast_enabled():
+        return None
+    return _ThetaLinearFn.apply(x2d, theta2d, bias,
+                                bool(k2) and theta2d.shape[1] % 32 == 0)
 
 
 def adaptive_linear_1x1(x2d: torch.Tensor, gw2d: torch.Tensor,
@@ -1078,14 +1140,17 @@ class _Conv3x3Fn(torch.autograd.Function):
         n, c, h, w = x_bf.shape
         k = weight.shape[0]
         hand = _conv_impl() == "hand"
-        if hand:
+        if weight.dtype == torch.bfloat16 and atten is None and aw is None:
+            # a ready bf16 θ (the head epoch's live θ): no copy-compose
+            theta = weight.detach()
+        else:
             theta = compose_theta_bf16(ext, weight, atten, aw)  # plain CL θ
+        if hand:
             y = torch.empty(n, k, h, w, device=x.device, dtype=torch.bfloat16,
                             memory_format=torch.channels_last)
             ext.conv3x3_img_fwd_ldsw(x_bf.data_ptr(), theta.data_ptr(),
                                      y.data_ptr(), n, h, w, c, k, _stream())
         else:
-            theta = compose_theta_bf16(ext, weight, atten, aw)
             y = torch.nn.functional.conv2d(x_bf, theta, padding=1)
         # the lib dgrad reuses the forward's θ — composing twice per step
         # cost ~1.2 ms/round
@@ -1155,11 +1220,16 @@ class _Conv3x3Fn(torch.autograd.Function):
                 dw = (part[0] + part[1]).view(k, 3, 3, c).permute(0, 3, 1, 2)
             else:
                 dw = torch.nn.grad.conv2d_weight(
-                    x_bf, (k, c, 3, 3), dy_bf, padding=1).to(torch.float32)
+                    x_bf, (k, c, 3, 3), dy_bf, padding=1)
+            # fp32 for aw (identity composition) and fp32 weights; a bf16
+            # weight (the live θ) takes the bf16 wgrad as it is — no cast pass
+            want = torch.float32 if ctx.needs_input_grad[3] else ctx.w_dtype
+            if dw.dtype != want:
+                dw = dw.to(want)
             if ctx.needs_input_grad[3]:
-                d_aw = dw              # identity composition, fp32 direct
+                d_aw = dw
             else:
-                d_weight = dw if ctx.w_dtype == torch.float32 else dw.to(ctx.w_dtype)
+                d_weight = dw
         return dx, d_weight, None, d_aw
 
 
@@ -1214,3 +1284,166 @@ def conv3x3_fwd_nhwc(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     ext.conv3x3_fwd(x.data_ptr(), wcl.float().data_ptr(), out.data_ptr(),
                     n, h, w, c, k, _stream())
     return out
+
+
+# ---------------------------------------------------------------------------
+# one-pass FedSTIL head update (head_step.hip)
+# ---------------------------------------------------------------------------
+
+HEAD_STEP_CHUNK = 1 << 14
+_HS_GRAD_BF16, _HS_VEC, _HS_THETA, _HS_ATTEN_VEC = 1, 2, 4, 8
+
+
+def _same_layout(t: torch.Tensor, like: torch.Tensor) -> bool:
+    """Same shape and the same PHYSICAL layout: strides compared on every
+    dim of extent > 1 (a size-1 dim's stride is arbitrary)."""
+    return t.shape == like.shape and all(
+        a == b for a, b, n in zip(t.stride(), like.stride(), like.shape)
+        if n > 1)
+
+
+def head_step_partials(rows) -> int:
+    """Number of drift partials a head_step over `rows` writes."""
+    return sum(-(-r["aw"].numel() // HEAD_STEP_CHUNK) for r in rows)
+
+
+def _head_step_geometry(aw: torch.Tensor):
+    """(L, inner): atten broadcasts over the LOGICAL last dim, whose
+    physical index is (i / inner) % L — inner = C for channels-last
+    [K][kh][kw][C] storage, 1 when the last dim is also physically last."""
+    if aw.dim() < 1 or aw.numel() == 0:
+        raise ValueError("head_step: empty adaptive weight")
+    if aw.is_contiguous():
+        return aw.shape[-1], 1
+    if aw.dim() == 4 and aw.is_contiguous(memory_format=torch.channels_last):
+        return aw.shape[-1], aw.shape[1]
+    raise ValueError("head_step: adaptive weight is neither contiguous nor "
+                     f"channels-last dense (strides {aw.stride()})")
+
+
+def _head_step_row(r: Dict, partial0: int):
+    aw = r["aw"]
+    if not aw.is_cuda or aw.dtype != torch.float32:
+        raise TypeError("head_step: aw must be a CUDA fp32 tensor")
+    L, inner = _head_step_geometry(aw)
+    for k in ("aw0", "m", "v", "dw"):
+        t = r.get(k)
+        if t is None:
+            raise ValueError(f"head_step: missing '{k}' (null pointer)")
+        if not t.is_cuda or t.device != aw.device:
+            raise TypeError(f"head_step: '{k}' is not on aw's device")
+        if t.numel() != aw.numel() or not _same_layout(t, aw):
+            raise ValueError(
+                f"head_step: '{k}' {tuple(t.shape)}/{t.stride()} does not "
+                f"match aw's layout {tuple(aw.shape)}/{aw.stride()}")
+        if k == "dw":
+            if t.dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError("head_step: dw must be fp32 or bf16")
+        elif t.dtype != torch.float32:
+            raise TypeError(f"head_step: '{k}' must be fp32")
+    step = r.get("step")
+    if (step is None or not step.is_cuda or step.dtype != torch.float32
+            or step.numel() != 1):
+        raise TypeError("head_step: step must be a CUDA fp32 scalar tensor")
+    dw = r["dw"]
+    flags = _HS_GRAD_BF16 if dw.dtype == torch.bfloat16 else 0
+    gw, atten, theta = r.get("gw"), r.get("atten"), r.get("theta")
+    has_theta = theta is not None
+    if has_theta:
+        if gw is None or atten is None:
+            raise ValueError("head_step: theta needs gw and atten "
+                             "(null pointer)")
+        if (gw.dtype != torch.float32 or gw.device != aw.device
+                or not _same_layout(gw, aw)):
+            raise ValueError("head_step: gw does not match aw's layout")
+        if (theta.dtype != torch.bfloat16 or theta.device != aw.device
+                or not _same_layout(theta, aw)):
+            raise ValueError("head_step: theta must be bf16 in aw's layout")
+        if (atten.dtype != torch.float32 or atten.device != aw.device
+                or not atten.is_contiguous() or atten.numel() != L):
+            raise ValueError("head_step: atten must be a contiguous fp32 "
+                             f"vector of the last weight dim ({L})")
+        flags |= _HS_THETA
+    # float4 path only for 16-byte rows whose 4-runs stay inside one
+    # atten-broadcast segment (as compose2_kernel); scalar path otherwise
+    galign = 8 if dw.dtype == torch.bfloat16 else 16
+    vec = (all(r[k].data_ptr() % 16 == 0 for k in ("aw", "aw0", "m", "v"))
+           and dw.data_ptr() % galign == 0)
+    if vec and has_theta:
+        vec = gw.data_ptr() % 16 == 0 and theta.data_ptr() % 8 == 0
+        if vec and inner == 1 and L > 1 and L % 4 == 0 \
+                and atten.data_ptr() % 16 == 0:
+            flags |= _HS_ATTEN_VEC
+        elif not (L == 1 or inner % 4 == 0):
+            vec = False
+    if vec:
+        flags |= _HS_VEC
+    return [aw.data_ptr(), r["aw0"].data_ptr(), dw.data_ptr(),
+            gw.data_ptr() if has_theta else 0,
+            atten.data_ptr() if has_theta else 0,
+            r["m"].data_ptr(), r["v"].data_ptr(),
+            theta.data_ptr() if has_theta else 0, step.data_ptr(),
+            aw.numel(), L, inner, flags, partial0]
+
+
+def _head_step_cpu(rows, partials, lr, beta1, beta2, weight_decay, eps, lam):
+    off = 0
+    partials.zero_()
+    for r in rows:
+        aw = r["aw"]
+        a, m1, v1, theta, drift = ref.head_step_reference(
+            aw, r["aw0"], r["dw"], r["m"], r["v"], r["step"], lr, beta1,
+            beta2, weight_decay, eps, lam, r.get("gw") if r.get("theta")
+            is not None else None, r.get("atten"))
+        aw.copy_(a)
+        r["m"].copy_(m1)
+        r["v"].copy_(v1)
+        if theta is not None:
+            r["theta"].copy_(theta)
+        partials[off] = drift
+        off += -(-aw.numel() // HEAD_STEP_CHUNK)
+
+
+@torch.no_grad()
+def head_step(rows, partials: torch.Tensor, lr: float, beta1: float,
+              beta2: float, weight_decay: float, eps: float,
+              lam: float) -> None:
+    """One fused FedSTIL head step over a list of adaptive weights.
+
+    rows: dicts with aw, aw0, dw (fp32 or bf16 gradient), m, v (Adam
+    moments, torch's layout), step (device fp32 count) and optionally
+    gw + atten + theta (bf16 output: the next step's composed weight).
+    Advances every step count by one, then — in ONE kernel pass per element
+    — adds the L1-drift subgradient λ·sign(aw − aw0) to dw, applies torch's
+    original-mode Adam and emits θ; `partials` (fp64,
+    head_step_partials(rows) entries) receives per-block Σ|aw − aw0| of the
+    pre-update weights, so partials.sum() is the drift value.
+
+    Every row is validated before anything is launched; a violated check
+    raises.  CPU tensors run head_step_reference."""
+    rows = list(rows)
+    if not rows:
+        raise ValueError("head_step: empty tensor table")
+    need = head_step_partials(rows)
+    if (partials.dtype != torch.float64 or partials.numel() < need
+            or not partials.is_contiguous()
+            or partials.device != rows[0]["aw"].device):
+        raise ValueError(f"head_step: partials must be a contiguous fp64 "
+                         f"tensor of ≥ {need} entries on aw's device")
+    if not rows[0]["aw"].is_cuda:
+        torch._foreach_add_([r["step"] for r in rows], 1)
+        _head_step_cpu(rows, partials, lr, beta1, beta2, weight_decay, eps,
+                       lam)
+        return
+    ext = _ext_or_raise("head_step")
+    if ext is None:
+        raise RuntimeError("head_step has no eager GPU path")
+    table, off = [], 0
+    for r in rows:
+        table.append(_head_step_row(r, off))
+        off += -(-r["aw"].numel() // HEAD_STEP_CHUNK)
+    assert ext.head_step_chunk() == HEAD_STEP_CHUNK
+    torch._foreach_add_([r["step"] for r in rows], 1)
+    ext.head_step(table, partials.data_ptr(), partials.numel(), float(lr),
+                  float(beta1), float(beta2), float(weight_decay), float(eps),
+                  float(lam), _stream())

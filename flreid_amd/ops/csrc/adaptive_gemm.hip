@@ -33,11 +33,18 @@ constexpr int AG_PAD = 2;     // bf16 pad per LDS row
 struct Prefetch {
   ushort4 xr[4];              // 4×(4 bf16) of the x tile
   float4 gr[2], ar[2];        // 2×float4 of gw / aw
+  ushort4 tr[2];              // PRE: 2×(4 bf16) of the ready θ
 };
 
+// PRE = true: θ arrives precomposed in bf16 (TH, [N, K] — the live θ the
+// head_step kernel keeps current during a head epoch); the prologue is a
+// plain bf16 load and GW/AW/ATTEN are unused.  Same tile loop and the same
+// bf16 θ values as the composing prologue, so the output is bit-identical.
+template <bool PRE>
 __global__ __launch_bounds__(128) void adaptive_linear_fwd_kernel(
     const __hip_bfloat16* __restrict__ X, const float* __restrict__ GW,
     const float* __restrict__ AW, const float* __restrict__ ATTEN,
+    const __hip_bfloat16* __restrict__ TH,
     const float* __restrict__ BIAS, __hip_bfloat16* __restrict__ OUT,
     int M, int N, int K) {
   __shared__ __hip_bfloat16 lx[2][AG_BM][AG_BK + AG_PAD];
@@ -65,8 +72,12 @@ __global__ __launch_bounds__(128) void adaptive_linear_fwd_kernel(
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int64_t base = (int64_t)(n0 + lr0 + 16 * i) * K + k0 + lc4;
-        p.gr[i] = *(const float4*)(GW + base);
-        p.ar[i] = AW ? *(const float4*)(AW + base) : float4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (PRE) {
+          p.tr[i] = *(const ushort4*)(TH + base);
+        } else {
+          p.gr[i] = *(const float4*)(GW + base);
+          p.ar[i] = AW ? *(const float4*)(AW + base) : float4{0.f, 0.f, 0.f, 0.f};
+        }
       }
     } else {
 #pragma unroll
@@ -82,13 +93,19 @@ __global__ __launch_bounds__(128) void adaptive_linear_fwd_kernel(
       for (int i = 0; i < 2; ++i) {
         const int nr = n0 + lr0 + 16 * i;
         float4 g = {0.f, 0.f, 0.f, 0.f}, a = {0.f, 0.f, 0.f, 0.f};
+        ushort4 th = {0, 0, 0, 0};
         if (nr < N) {
           const int64_t base = (int64_t)nr * K + k0 + lc4;
-          g = *(const float4*)(GW + base);
-          if (AW) a = *(const float4*)(AW + base);
+          if constexpr (PRE) {
+            th = *(const ushort4*)(TH + base);
+          } else {
+            g = *(const float4*)(GW + base);
+            if (AW) a = *(const float4*)(AW + base);
+          }
         }
         p.gr[i] = g;
         p.ar[i] = a;
+        p.tr[i] = th;
       }
     }
   };
@@ -101,6 +118,17 @@ __global__ __launch_bounds__(128) void adaptive_linear_fwd_kernel(
       dst[1] = *(const __hip_bfloat16*)&p.xr[i].y;
       dst[2] = *(const __hip_bfloat16*)&p.xr[i].z;
       dst[3] = *(const __hip_bfloat16*)&p.xr[i].w;
+    }
+    if constexpr (PRE) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        __hip_bfloat16* dst = &lth[buf][lr0 + 16 * i][lc4];
+        dst[0] = *(const __hip_bfloat16*)&p.tr[i].x;
+        dst[1] = *(const __hip_bfloat16*)&p.tr[i].y;
+        dst[2] = *(const __hip_bfloat16*)&p.tr[i].z;
+        dst[3] = *(const __hip_bfloat16*)&p.tr[i].w;
+      }
+      return;
     }
     float at[4] = {1.f, 1.f, 1.f, 1.f};
     if (ATTEN) {
@@ -184,9 +212,30 @@ extern "C" void flreid_adaptive_linear_fwd(
   }
   dim3 grid((M + AG_BM - 1) / AG_BM, (N + AG_BN - 1) / AG_BN);
   dim3 block(128);
-  hipLaunchKernelGGL((adaptive_linear_fwd_kernel), grid, block, 0, stream,
-                     (const __hip_bfloat16*)X, GW, AW, ATTEN, BIAS,
+  hipLaunchKernelGGL((adaptive_linear_fwd_kernel<false>), grid, block, 0,
+                     stream, (const __hip_bfloat16*)X, GW, AW, ATTEN,
+                     (const __hip_bfloat16*)nullptr, BIAS,
                      (__hip_bfloat16*)OUT, M, N, K);
+  HIP_CHECK(hipGetLastError());
+}
+
+// y = x · θᵀ + bias on a ready bf16 θ [N, K]
+extern "C" void flreid_theta_linear_fwd(const void* X, const void* TH,
+                                        const float* BIAS, void* OUT, int M,
+                                        int N, int K, hipStream_t stream) {
+  if (K % AG_BK != 0) {
+    throw std::runtime_error("theta_linear_fwd: K must be a multiple of 32");
+  }
+  if (!X || !TH || !OUT) {
+    throw std::runtime_error("theta_linear_fwd: null pointer");
+  }
+  dim3 grid((M + AG_BM - 1) / AG_BM, (N + AG_BN - 1) / AG_BN);
+  dim3 block(128);
+  hipLaunchKernelGGL((adaptive_linear_fwd_kernel<true>), grid, block, 0,
+                     stream, (const __hip_bfloat16*)X, (const float*)nullptr,
+                     (const float*)nullptr, (const float*)nullptr,
+                     (const __hip_bfloat16*)TH, BIAS, (__hip_bfloat16*)OUT,
+                     M, N, K);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -6,8 +6,11 @@
 // stay ordered with PyTorch work on the same stream.
 
 #include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
 
 #include <cstdint>
+#include <stdexcept>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -105,6 +108,13 @@ extern "C" void flreid_decomposed_bwd(const void*, int, const float*,
                                       int64_t, int64_t, int64_t, int64_t, int,
                                       int, float, float, int, int, int,
                                       hipStream_t);
+extern "C" void flreid_theta_linear_fwd(const void*, const void*,
+                                        const float*, void*, int, int, int,
+                                        hipStream_t);
+extern "C" int flreid_head_step_chunk();
+extern "C" void flreid_head_step(const int64_t*, int, double*, int64_t,
+                                 double, double, double, double, double,
+                                 float, hipStream_t);
 }  // namespace flreid
 
 namespace py = pybind11;
@@ -405,5 +415,34 @@ PYBIND11_MODULE(_flreid_hip, m) {
               (float*)dmask_part, (float*)datten_part, rows, C, S, KB,
               channels_last, train, lambda_l1, lambda_mask, need_aw,
               need_mask, need_atten, as_stream(stream));
+        });
+
+  m.def("theta_linear_fwd",
+        [](uintptr_t x, uintptr_t theta, uintptr_t bias, uintptr_t out, int M,
+           int N, int K, uintptr_t stream) {
+          flreid::flreid_theta_linear_fwd((const void*)x, (const void*)theta,
+                                          (const float*)bias, (void*)out, M,
+                                          N, K, as_stream(stream));
+        });
+
+  m.def("head_step_chunk", []() { return flreid::flreid_head_step_chunk(); });
+
+  // rows: one 14-int64 row per adaptive weight (see head_step.hip); the
+  // table is validated in full before anything is launched
+  m.def("head_step",
+        [](const std::vector<std::vector<int64_t>>& rows, uintptr_t partials,
+           int64_t n_partials, double lr, double beta1, double beta2,
+           double weight_decay, double eps, float lambda, uintptr_t stream) {
+          std::vector<int64_t> flat;
+          flat.reserve(rows.size() * 14);
+          for (const auto& r : rows) {
+            if (r.size() != 14)
+              throw std::invalid_argument("head_step: rows need 14 fields");
+            flat.insert(flat.end(), r.begin(), r.end());
+          }
+          flreid::flreid_head_step(flat.data(), (int)rows.size(),
+                                   (double*)partials, n_partials, lr, beta1,
+                                   beta2, weight_decay, eps, lambda,
+                                   as_stream(stream));
         });
 }

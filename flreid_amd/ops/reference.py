@@ -224,6 +224,46 @@ def adaptive_compose(global_weight: torch.Tensor, atten: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# one-pass FedSTIL head update (head_step.hip)
+# ---------------------------------------------------------------------------
+
+def head_step_reference(aw: torch.Tensor, aw0: torch.Tensor, dw: torch.Tensor,
+                        m: torch.Tensor, v: torch.Tensor, step,
+                        lr: float, beta1: float, beta2: float,
+                        weight_decay: float, eps: float, lam: float,
+                        gw: Optional[torch.Tensor] = None,
+                        atten: Optional[torch.Tensor] = None):
+    """One FedSTIL head step of one adaptive weight in fp64 torch ops:
+    L1-drift subgradient λ·sign(aw − aw0) added to the task gradient `dw`,
+    torch's original-mode Adam (L2 weight decay folded into the gradient,
+    bias corrections from `step`, the count AFTER this step), and — when
+    gw/atten are given — the next step's θ = atten ⊙_lastdim gw + aw_new.
+
+    Pure: returns fp64 (aw_new, m_new, v_new, theta or None, drift), where
+    drift = Σ|aw − aw0| of the PRE-update weights.  λ enters as the fp32
+    value the autograd chain multiplies the sign by."""
+    f64 = torch.float64
+    a, a0, g = aw.detach().to(f64), aw0.detach().to(f64), dw.detach().to(f64)
+    m1, v1 = m.detach().to(f64), v.detach().to(f64)
+    lam32 = float(torch.tensor(lam, dtype=torch.float32))
+    d = a - a0
+    drift = d.abs().sum()
+    g = g + lam32 * torch.sign(d)
+    if weight_decay != 0:
+        g = g + weight_decay * a
+    m1 = beta1 * m1 + (1 - beta1) * g
+    v1 = beta2 * v1 + (1 - beta2) * g * g
+    t = float(step)
+    bc1 = 1 - beta1 ** t
+    bc2_sqrt = (1 - beta2 ** t) ** 0.5
+    a = a - (lr / bc1) * m1 / (v1.sqrt() / bc2_sqrt + eps)
+    theta = None
+    if gw is not None:
+        theta = atten.detach().to(f64) * gw.detach().to(f64) + a
+    return a, m1, v1, theta, drift
+
+
+# ---------------------------------------------------------------------------
 # FedWeIT decomposed-layer composition (ref:methods/fedweit.py:122-136)
 # ---------------------------------------------------------------------------
 
