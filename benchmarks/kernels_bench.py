@@ -145,6 +145,40 @@ def bench_head_step(results, n):
             lambda: x @ cls["theta"].t(), n)
 
 
+DRIFT_SHAPES = [(512, 512, 3, 3), (2048, 512, 1, 1), (512, 2048, 1, 1),
+                (8000, 2048)] * 3
+
+
+def bench_penalty(results, n):
+    """Multi-tensor quadratic penalty fwd+bwd (penalty.hip) vs the eager
+    reference over the layer4+classifier shape list of the drift entry, at
+    S = 1 (EWC/MAS) and S = 3 (FedCurv with two other clients).  GBps uses
+    the fused form's traffic model: 2S + 1 weight-sized reads forward, the
+    same reads and the gradient write backward — 4S + 3 passes."""
+    params = {str(i): torch.randn(s, device="cuda", requires_grad=True)
+              for i, s in enumerate(DRIFT_SHAPES)}
+    numel = sum(p.numel() for p in params.values())
+    all_sets = [({k: torch.randn_like(p) for k, p in params.items()},
+                 {k: torch.rand_like(p) for k, p in params.items()})
+                for _ in range(3)]
+
+    def run(fn, sets):
+        loss = fn(params, sets) * 100.0
+        loss.backward()
+        for p in params.values():
+            p.grad = None
+
+    for s in (1, 3):
+        sets = all_sets[:s]
+        results[f"penalty_fused_s{s}"] = bench(
+            lambda: run(ops.quadratic_penalty_sets, sets), n)
+        results[f"penalty_eager_s{s}"] = bench(
+            lambda: run(ref.quadratic_penalty_sets, sets), n)
+        results[f"penalty_fused_s{s}_GBps"] = round(
+            numel * 4 * (4 * s + 3)
+            / (results[f"penalty_fused_s{s}"] / 1e3) / 1e9, 0)
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
@@ -159,11 +193,17 @@ def main():
                    help="run only the FedWeIT composition entry")
     p.add_argument("--head-step-only", action="store_true",
                    help="run only the FedSTIL one-pass head update entry")
+    p.add_argument("--penalty-only", action="store_true",
+                   help="run only the quadratic-penalty entry")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
 
+    if args.penalty_only:
+        bench_penalty(results, n)
+        report(results)
+        return
     if args.head_step_only:
         bench_head_step(results, n)
         report(results)
@@ -254,8 +294,7 @@ def main():
         results[f"bn_train_c{c}_miopen"] = bench(miopen_bn, n)
 
     # fused multi-tensor L1 drift (FedSTIL per-step regulariser) vs _foreach
-    shapes = [(512, 512, 3, 3), (2048, 512, 1, 1), (512, 2048, 1, 1),
-              (8000, 2048)] * 3
+    shapes = DRIFT_SHAPES
     params = [torch.randn(s, device="cuda", requires_grad=True)
               for s in shapes]
     anchors = [torch.randn(s, device="cuda") for s in shapes]
@@ -275,6 +314,8 @@ def main():
 
     results["drift_fused"] = bench(fused_drift, n)
     results["drift_foreach"] = bench(foreach_drift, n)
+
+    bench_penalty(results, n)
 
     report(results)
 

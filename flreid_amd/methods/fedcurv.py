@@ -33,11 +33,12 @@ class Model(ImportanceModel):
         super().__init__(net, operator, lambda_penalty, **kwargs)
 
     def penalty(self) -> torch.Tensor:
-        own = ops.quadratic_penalty(self.params, self.params_old,
-                                    self.precision_matrices)
-        for importance, params in self.other_precision_matrices:
-            own = own + ops.quadratic_penalty(self.params, params, importance)
-        return self.lambda_penalty * own
+        # own Fisher/anchors + one set per other client, p read once
+        sets = [(self.params_old, self.precision_matrices)] + [
+            (params, importance)
+            for importance, params in self.other_precision_matrices]
+        return self.lambda_penalty * ops.quadratic_penalty_sets(
+            self.params, sets)
 
     def _move_aux(self, fn) -> None:
         super()._move_aux(fn)

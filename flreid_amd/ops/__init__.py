@@ -14,7 +14,8 @@ the fp32 reference implementation (tests/test_ops_gpu.py).
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional
+from collections import OrderedDict
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -356,9 +357,9 @@ def importance_update(importance: Dict[str, torch.Tensor],
 # ---------------------------------------------------------------------------
 
 kl_distance = ref.kl_distance
-quadratic_penalty = ref.quadratic_penalty
 l1_drift_fused = ref.l1_drift_fused
-# l1_drift is defined below: fused HIP multi-tensor path on GPU
+# l1_drift and quadratic_penalty(_sets) are defined below: fused HIP
+# multi-tensor paths on GPU
 
 
 class _KdLossFn(torch.autograd.Function):
@@ -827,6 +828,176 @@ def l1_drift(pairs) -> torch.Tensor:
         anchors = [a for _, a in pairs]
         return _L1DriftHipFn.apply(meta, len(params), *params, *anchors)
     return ref.l1_drift_fused(pairs)
+
+
+# ---------------------------------------------------------------------------
+# fused multi-tensor quadratic penalty — EWC/MAS/FedCurv/FedProx (penalty.hip)
+# ---------------------------------------------------------------------------
+
+_PENALTY_META_CAP = 8
+_PENALTY_META: "OrderedDict" = OrderedDict()
+
+
+def _dense(t: torch.Tensor) -> bool:
+    """Non-overlapping and dense: the storage run [data_ptr, data_ptr + numel)
+    holds every element exactly once (contiguous, channels-last, permuted)."""
+    expect = 1
+    for stride, size in sorted((s, n) for n, s in zip(t.shape, t.stride())
+                               if n > 1):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def _penalty_plan(params, sets):
+    """([(p, [a_0, F_0, a_1, F_1, …])], padded_total) when every tensor of
+    the call fits the kernel, else None.  A set's absent name contributes
+    (None, None); importance=None contributes (a, None).  Names no set knows
+    are left out (no term, no gradient — as the reference)."""
+    rows, total, dev = [], 0, None
+    for n, p in params.items():
+        slots, present = [], False
+        for anchors, importance in sets:
+            if n not in anchors:
+                slots += [None, None]
+                continue
+            present = True
+            slots += [anchors[n],
+                      importance[n] if importance is not None else None]
+        if not present:
+            continue
+        if dev is None:
+            dev = p.device
+        if (not p.is_cuda or p.device != dev or p.dtype != torch.float32
+                or p.numel() == 0 or p.data_ptr() % 16 or not _dense(p)):
+            return None
+        for t in slots:
+            if t is not None and (
+                    not isinstance(t, torch.Tensor) or t.device != dev
+                    or t.dtype != torch.float32 or t.data_ptr() % 16
+                    or not _same_layout(t, p)):
+                return None
+        rows.append((p, slots))
+        total += -(-p.numel() // 4) * 4     # float4 stores: quad-aligned slots
+    if not rows or total >= 2 ** 31:
+        return None
+    return rows, total
+
+
+def _penalty_meta(rows, n_sets: int, total: int, chunk: int):
+    """(ptr_table, chunk_table, S, flat_offsets, padded_total) on device,
+    cached on the storages.  Unlike _DRIFT_META the cache is a small LRU: the
+    penalty methods re-clone their anchors every round, so the keys keep
+    changing, and none of them replays a captured graph that could hold a
+    table (an autograd node in flight keeps its own reference)."""
+    ptr_rows = [(p.data_ptr(), *(0 if t is None else t.data_ptr()
+                                 for t in slots)) for p, slots in rows]
+    key = (n_sets, rows[0][0].device,
+           tuple((p.numel(), *pr) for (p, _), pr in zip(rows, ptr_rows)))
+    meta = _PENALTY_META.get(key)
+    if meta is not None:
+        _PENALTY_META.move_to_end(key)
+        return meta
+    chunk_rows, offsets = [], []
+    flat_off = 0
+    for i, (p, _) in enumerate(rows):
+        n = p.numel()
+        offsets.append(flat_off)
+        off = 0
+        while off < n:
+            ln = min(chunk, n - off)
+            chunk_rows.append((i, off, ln, flat_off + off))
+            off += ln
+        flat_off += -(-n // 4) * 4
+    assert flat_off == total
+    dev = rows[0][0].device
+    meta = (torch.tensor(ptr_rows, dtype=torch.int64, device=dev),
+            torch.tensor(chunk_rows, dtype=torch.int32, device=dev),
+            n_sets, offsets, total)
+    _PENALTY_META[key] = meta
+    while len(_PENALTY_META) > _PENALTY_META_CAP:
+        _PENALTY_META.popitem(last=False)
+    return meta
+
+
+class _QuadraticPenaltyHipFn(torch.autograd.Function):
+    """Fused multi-tensor Σ_s Σ F_s·(p − a_s)² (ops/csrc/penalty.hip): the
+    forward reads p once and every set and writes the per-chunk partials; the
+    backward reads them again and writes the gradient — in the eager chain's
+    own rounding, so the bits are the reference's — into one flat buffer,
+    handed out as per-tensor views in each param's own shape and strides."""
+
+    @staticmethod
+    def forward(ctx, meta, consts, *params):
+        ext = _ext_or_raise("penalty_fwd")
+        ptrs, chunks, n_sets, offsets, total = meta
+        partials = torch.empty(chunks.shape[0], device=params[0].device,
+                               dtype=torch.float32)
+        ext.penalty_fwd(ptrs.data_ptr(), chunks.data_ptr(), n_sets,
+                        partials.data_ptr(), chunks.shape[0], _stream())
+        # params are saved for autograd's in-place-modification check; the
+        # tables and the constants they point to must outlive the cache entry
+        ctx.save_for_backward(*params)
+        ctx.meta = meta
+        ctx.consts = consts
+        return partials.sum()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ext = _ext_or_raise("penalty_bwd")
+        params = ctx.saved_tensors
+        ptrs, chunks, n_sets, offsets, total = ctx.meta
+        g = grad_out.to(torch.float32).contiguous()
+        flat = torch.empty(total, device=g.device, dtype=torch.float32)
+        ext.penalty_bwd(ptrs.data_ptr(), chunks.data_ptr(), n_sets,
+                        g.data_ptr(), flat.data_ptr(), chunks.shape[0],
+                        _stream())
+        views = [torch.as_strided(flat, p.shape, p.stride(), off)
+                 for p, off in zip(params, offsets)]
+        return (None, None, *views)
+
+
+def quadratic_penalty_sets(
+        params: Dict[str, torch.Tensor],
+        sets: Sequence[Tuple[Dict[str, torch.Tensor],
+                             Optional[Dict[str, torch.Tensor]]]],
+) -> torch.Tensor:
+    """Σ_s Σ_n F_s[n]·(p[n] − a_s[n])² over (anchors, importance) sets; p read once.
+
+    importance=None in a set is unit importance (FedProx); a name a set's
+    anchors lack is skipped for that set.  Gradients flow to params only
+    (anchors and importance are constants) and carry the eager reference's
+    bits; the value differs from it by summation order.  Fused HIP path on GPU when every
+    tensor of the call is fp32, 16-byte aligned and p / a_s / F_s share one
+    dense layout per name (contiguous, channels-last, …) and the extension is
+    built; otherwise — CPU, any ineligible tensor, or
+    FLREID_NO_FUSED_PENALTY=1 — the whole call runs the eager reference."""
+    sets = list(sets)
+    first = next(iter(params.values()), None)
+    if (sets and first is not None and first.is_cuda
+            and os.environ.get("FLREID_NO_FUSED_PENALTY", "0") != "1"):
+        plan = _penalty_plan(params, sets)
+        if plan is not None:
+            ext = _ext_or_raise("penalty_fwd")
+            if ext is not None:
+                rows, total = plan
+                meta = _penalty_meta(rows, len(sets), total,
+                                     ext.penalty_chunk())
+                consts = tuple(t for _, slots in rows for t in slots
+                               if t is not None)
+                return _QuadraticPenaltyHipFn.apply(
+                    meta, consts, *(p for p, _ in rows))
+    return ref.quadratic_penalty_sets(params, sets)
+
+
+def quadratic_penalty(params: Dict[str, torch.Tensor],
+                      anchors: Dict[str, torch.Tensor],
+                      importance: Optional[Dict[str, torch.Tensor]] = None,
+                      ) -> torch.Tensor:
+    """Σ F·(p − p_anchor)² — EWC/MAS penalty; importance=None is the FedProx
+    proximal term.  One-set form of quadratic_penalty_sets."""
+    return quadratic_penalty_sets(params, [(anchors, importance)])
 
 
 class _BnTrain2dFn(torch.autograd.Function):

@@ -95,6 +95,12 @@ extern "C" void flreid_drift_fwd(const int64_t*, const int*, float*, int,
                                  hipStream_t);
 extern "C" void flreid_drift_bwd(const int64_t*, const int*, const float*,
                                  float*, int, hipStream_t);
+extern "C" int flreid_penalty_chunk();
+extern "C" int flreid_penalty_block();
+extern "C" void flreid_penalty_fwd(const int64_t*, const int*, int, float*,
+                                   int, hipStream_t);
+extern "C" void flreid_penalty_bwd(const int64_t*, const int*, int,
+                                   const float*, float*, int, hipStream_t);
 extern "C" void flreid_decomposed_plan(int64_t, int64_t, int64_t, int,
                                        int64_t*, int64_t*);
 extern "C" void flreid_decomposed_fwd(const float*, const float*,
@@ -369,6 +375,27 @@ PYBIND11_MODULE(_flreid_hip, m) {
           flreid::flreid_drift_bwd((const int64_t*)ptrs, (const int*)chunks,
                                    (const float*)gscale, (float*)flat_grad,
                                    n_chunks, as_stream(stream));
+        });
+
+  m.def("penalty_chunk", []() { return flreid::flreid_penalty_chunk(); });
+  m.def("penalty_block", []() { return flreid::flreid_penalty_block(); });
+
+  m.def("penalty_fwd",
+        [](uintptr_t ptrs, uintptr_t chunks, int S, uintptr_t partials,
+           int n_chunks, uintptr_t stream) {
+          flreid::flreid_penalty_fwd((const int64_t*)ptrs, (const int*)chunks,
+                                     S, (float*)partials, n_chunks,
+                                     as_stream(stream));
+        });
+
+  // gscale: device pointer to the upstream gradient (one float)
+  m.def("penalty_bwd",
+        [](uintptr_t ptrs, uintptr_t chunks, int S, uintptr_t gscale,
+           uintptr_t flat_grad, int n_chunks, uintptr_t stream) {
+          flreid::flreid_penalty_bwd((const int64_t*)ptrs, (const int*)chunks,
+                                     S, (const float*)gscale,
+                                     (float*)flat_grad, n_chunks,
+                                     as_stream(stream));
         });
 
   m.def("triplet_bwd",

@@ -172,6 +172,19 @@ def quadratic_penalty(params: Dict[str, torch.Tensor],
     return total
 
 
+def quadratic_penalty_sets(params: Dict[str, torch.Tensor], sets) -> torch.Tensor:
+    """Σ_s quadratic_penalty(params, anchors_s, importance_s) over
+    (anchors, importance) sets — FedCurv's own + other-client terms
+    (ref:methods/fedcurv.py:79-86)."""
+    total = None
+    for anchors, importance in sets:
+        s = quadratic_penalty(params, anchors, importance)
+        total = s if total is None else total + s
+    if total is None:
+        total = torch.zeros((), device=next(iter(params.values())).device)
+    return total
+
+
 def l1_drift(pairs: Iterable[Tuple[torch.Tensor, torch.Tensor]]) -> torch.Tensor:
     """Σ |p − p₀| — FedSTIL sparsity/drift regulariser
     (ref:methods/fedstil.py:639-644)."""
