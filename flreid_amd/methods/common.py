@@ -182,14 +182,14 @@ class FusedHeadStep:
                     or not p.requires_grad or id(p) not in in_group
                     or not p.is_cuda or p.dtype != torch.float32
                     or a.dtype != torch.float32
-                    or not ops._same_layout(a, p)
+                    or not ops.same_layout(a, p)
                     or atten.shape != leaf.initial_global_weight_atten.shape):
                 return None
             try:
-                L, _inner = ops._head_step_geometry(p)
+                L, _inner = ops.atten_geometry(p)
             except ValueError:
                 return None
-            if (gw.dtype != torch.float32 or not ops._same_layout(gw, p)
+            if (gw.dtype != torch.float32 or not ops.same_layout(gw, p)
                     or atten.dtype != torch.float32
                     or not atten.is_contiguous() or atten.numel() != L):
                 live = False
@@ -213,7 +213,7 @@ class FusedHeadStep:
                     or step.dtype != torch.float32
                     or not all(torch.is_tensor(st.get(k))
                                and st[k].dtype == torch.float32
-                               and ops._same_layout(st[k], p)
+                               and ops.same_layout(st[k], p)
                                for k in ("exp_avg", "exp_avg_sq"))):
                 return None
             states.append(st)

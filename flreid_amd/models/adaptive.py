@@ -54,7 +54,7 @@ class _LiveThetaFn(torch.autograd.Function):
         live = ctx.live
         if g.dtype != torch.bfloat16:
             g = g.to(torch.bfloat16)
-        if not ops._same_layout(g, live.theta):
+        if not ops.same_layout(g, live.theta):
             # e.g. an NCHW-ordered conv2d_weight result for a channels-last θ
             g = torch.empty_like(live.theta).copy_(g)
         live.grad = g if live.grad is None else live.grad + g
@@ -83,7 +83,7 @@ def live_theta_scope(leaves, buffers):
     head epoch; detached on exit, exceptions included.  Nothing outside the
     scope ever reads the buffers (herding, validation, uploads and dispatch
     re-inits go through composed_weight), so a stale θ cannot be observed."""
-    ext = ops._ext_or_raise("compose2")
+    ext = ops.require_extension("compose2")
     try:
         for leaf, buf in zip(leaves, buffers):
             ops.compose_theta_bf16(ext, leaf.global_weight,

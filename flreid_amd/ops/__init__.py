@@ -45,7 +45,8 @@ def extension_available() -> bool:
     return _load_extension() is not None
 
 
-def _ext_or_raise(opname: str):
+def require_extension(opname: str):
+    """The built extension, or an error (None under FLREID_ALLOW_EAGER=1)."""
     ext = _load_extension()
     if ext is not None:
         return ext
@@ -68,6 +69,72 @@ def _dt(t: torch.Tensor) -> int:
     if t.dtype == torch.bfloat16:
         return _BF16
     raise TypeError(f"unsupported dtype {t.dtype}")
+
+
+# ---------------------------------------------------------------------------
+# layout helpers and the multi-tensor chunk table
+# ---------------------------------------------------------------------------
+
+def same_layout(t: torch.Tensor, like: torch.Tensor) -> bool:
+    """Same shape and the same PHYSICAL layout: strides compared on every
+    dim of extent > 1 (a size-1 dim's stride is arbitrary)."""
+    return t.shape == like.shape and all(
+        a == b for a, b, n in zip(t.stride(), like.stride(), like.shape)
+        if n > 1)
+
+
+def _dense(t: torch.Tensor) -> bool:
+    """Non-overlapping and dense: the storage run [data_ptr, data_ptr + numel)
+    holds every element exactly once (contiguous, channels-last, permuted)."""
+    expect = 1
+    for stride, size in sorted((s, n) for n, s in zip(t.shape, t.stride())
+                               if n > 1):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def atten_geometry(w: torch.Tensor) -> Tuple[int, int]:
+    """(L, inner): atten broadcasts over the LOGICAL last dim, whose
+    physical index is (i / inner) % L — inner = C for channels-last
+    [K][kh][kw][C] storage, 1 when the last dim is also physically last."""
+    if w.dim() < 1 or w.numel() == 0:
+        raise ValueError("atten_geometry: empty adaptive weight")
+    if w.is_contiguous():
+        return w.shape[-1], 1
+    if w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last):
+        return w.shape[-1], w.shape[1]
+    raise ValueError("atten_geometry: adaptive weight is neither contiguous "
+                     f"nor channels-last dense (strides {w.stride()})")
+
+
+def _fusable(t, like: Optional[torch.Tensor] = None) -> bool:
+    """What a multi-tensor kernel's float4 body needs: fp32 on a GPU, 16-byte
+    aligned, and dense — or, given `like`, on its device in its very layout."""
+    return (isinstance(t, torch.Tensor) and t.is_cuda
+            and t.dtype == torch.float32 and t.data_ptr() % 16 == 0
+            and (_dense(t) if like is None
+                 else t.device == like.device and same_layout(t, like)))
+
+
+def _chunk_table(numels: Sequence[int], chunk: int, pad_to: int = 1):
+    """(chunk_rows, flat_offsets, total): one (tensor, elem_offset, len,
+    flat_offset) row, i.e. one workgroup, per ≤ `chunk` elements; tensor i's
+    slot of the flat buffer starts at flat_offsets[i], `pad_to`-aligned."""
+    chunk_rows, offsets, flat_off = [], [], 0
+    for i, n in enumerate(numels):
+        offsets.append(flat_off)
+        chunk_rows += [(i, off, min(chunk, n - off), flat_off + off)
+                       for off in range(0, n, chunk)]
+        flat_off += -(-n // pad_to) * pad_to
+    return chunk_rows, offsets, flat_off
+
+
+# the names these had before they had callers outside ops/
+_ext_or_raise = require_extension
+_same_layout = same_layout
+_head_step_geometry = atten_geometry
 
 
 # ---------------------------------------------------------------------------
@@ -357,9 +424,6 @@ def importance_update(importance: Dict[str, torch.Tensor],
 # ---------------------------------------------------------------------------
 
 kl_distance = ref.kl_distance
-l1_drift_fused = ref.l1_drift_fused
-# l1_drift and quadratic_penalty(_sets) are defined below: fused HIP
-# multi-tensor paths on GPU
 
 
 class _KdLossFn(torch.autograd.Function):
@@ -761,16 +825,16 @@ class _L1DriftHipFn(torch.autograd.Function):
     into per-tensor grad views."""
 
     @staticmethod
-    def forward(ctx, meta, n_params, *tensors):
+    def forward(ctx, meta, *tensors):        # tensors: the params, the anchors
         ext = _ext_or_raise("drift")
         ptrs, chunks, sizes, total = meta
         partials = torch.empty(chunks.shape[0], device=tensors[0].device,
                                dtype=torch.float32)
         ext.drift_fwd(ptrs.data_ptr(), chunks.data_ptr(), partials.data_ptr(),
                       chunks.shape[0], _stream())
+        # the tables and the tensors they point to must outlive the caller's
         ctx.meta = meta
-        ctx.n_params = n_params
-        ctx.shapes = [t.shape for t in tensors[:n_params]]
+        ctx.tensors = tensors
         return partials.sum()
 
     @staticmethod
@@ -781,8 +845,8 @@ class _L1DriftHipFn(torch.autograd.Function):
         g = grad_out.to(torch.float32).contiguous()
         ext.drift_bwd(ptrs.data_ptr(), chunks.data_ptr(), g.data_ptr(),
                       flat.data_ptr(), chunks.shape[0], _stream())
-        views = [v.view(s) for v, s in zip(flat.split(sizes), ctx.shapes)]
-        return (None, None, *views, *([None] * ctx.n_params))
+        views = [v.view_as(p) for v, p in zip(flat.split(sizes), ctx.tensors)]
+        return (None, *views, *([None] * len(views)))
 
 
 def _drift_meta(pairs):
@@ -794,39 +858,29 @@ def _drift_meta(pairs):
     if meta is not None:
         return meta
     dev = pairs[0][0].device
-    ptr_rows, chunk_rows, sizes = [], [], []
-    flat_off = 0
-    for i, (p, a) in enumerate(pairs):
-        ptr_rows.append((p.data_ptr(), a.data_ptr()))
-        n = p.numel()
-        sizes.append(n)
-        off = 0
-        while off < n:
-            ln = min(_DRIFT_CHUNK, n - off)
-            chunk_rows.append((i, off, ln, flat_off + off))
-            off += ln
-        flat_off += n
-    ptrs = torch.tensor(ptr_rows, dtype=torch.int64, device=dev)
+    sizes = [p.numel() for p, _ in pairs]
+    chunk_rows, _, total = _chunk_table(sizes, _DRIFT_CHUNK)
+    ptrs = torch.tensor([(p.data_ptr(), a.data_ptr()) for p, a in pairs],
+                        dtype=torch.int64, device=dev)
     chunks = torch.tensor(chunk_rows, dtype=torch.int32, device=dev)
     # entries are never evicted: a captured hipGraph may hold the table
     # pointers for its lifetime, and each entry is only ~KBs
-    meta = (ptrs, chunks, sizes, flat_off)
+    meta = (ptrs, chunks, sizes, total)
     _DRIFT_META[key] = meta
     return meta
 
 
 def l1_drift(pairs) -> torch.Tensor:
-    """Σ |p − p₀| over drift pairs — fused HIP multi-tensor path on GPU
-    (fp32, contiguous), _foreach fallback elsewhere."""
+    """Σ |p − p₀| over drift pairs — fused HIP multi-tensor path on GPU when
+    every p and anchor is fp32, 16-byte aligned (float4 reads) and contiguous
+    (backward's grad views are) on one device; _foreach fallback elsewhere."""
     pairs = [(p, a.detach()) for p, a in pairs]
     if (pairs and pairs[0][0].is_cuda and extension_available()
-            and all(p.dtype == torch.float32 and p.is_contiguous()
-                    and a.dtype == torch.float32 and a.is_contiguous()
-                    and p.numel() == a.numel() for p, a in pairs)):
-        meta = _drift_meta(pairs)
-        params = [p for p, _ in pairs]
-        anchors = [a for _, a in pairs]
-        return _L1DriftHipFn.apply(meta, len(params), *params, *anchors)
+            and all(p.is_contiguous() and p.device == pairs[0][0].device
+                    and _fusable(p) and _fusable(a, p) for p, a in pairs)
+            and sum(p.numel() for p, _ in pairs) < 2 ** 31):   # int32 table
+        return _L1DriftHipFn.apply(_drift_meta(pairs), *(p for p, _ in pairs),
+                                   *(a for _, a in pairs))
     return ref.l1_drift_fused(pairs)
 
 
@@ -838,24 +892,12 @@ _PENALTY_META_CAP = 8
 _PENALTY_META: "OrderedDict" = OrderedDict()
 
 
-def _dense(t: torch.Tensor) -> bool:
-    """Non-overlapping and dense: the storage run [data_ptr, data_ptr + numel)
-    holds every element exactly once (contiguous, channels-last, permuted)."""
-    expect = 1
-    for stride, size in sorted((s, n) for n, s in zip(t.shape, t.stride())
-                               if n > 1):
-        if stride != expect:
-            return False
-        expect *= size
-    return True
-
-
 def _penalty_plan(params, sets):
     """([(p, [a_0, F_0, a_1, F_1, …])], padded_total) when every tensor of
     the call fits the kernel, else None.  A set's absent name contributes
     (None, None); importance=None contributes (a, None).  Names no set knows
     are left out (no term, no gradient — as the reference)."""
-    rows, total, dev = [], 0, None
+    rows, total = [], 0
     for n, p in params.items():
         slots, present = [], False
         for anchors, importance in sets:
@@ -867,17 +909,10 @@ def _penalty_plan(params, sets):
                       importance[n] if importance is not None else None]
         if not present:
             continue
-        if dev is None:
-            dev = p.device
-        if (not p.is_cuda or p.device != dev or p.dtype != torch.float32
-                or p.numel() == 0 or p.data_ptr() % 16 or not _dense(p)):
+        if (not _fusable(p) or p.numel() == 0
+                or (rows and p.device != rows[0][0].device)
+                or not all(t is None or _fusable(t, p) for t in slots)):
             return None
-        for t in slots:
-            if t is not None and (
-                    not isinstance(t, torch.Tensor) or t.device != dev
-                    or t.dtype != torch.float32 or t.data_ptr() % 16
-                    or not _same_layout(t, p)):
-                return None
         rows.append((p, slots))
         total += -(-p.numel() // 4) * 4     # float4 stores: quad-aligned slots
     if not rows or total >= 2 ** 31:
@@ -899,17 +934,8 @@ def _penalty_meta(rows, n_sets: int, total: int, chunk: int):
     if meta is not None:
         _PENALTY_META.move_to_end(key)
         return meta
-    chunk_rows, offsets = [], []
-    flat_off = 0
-    for i, (p, _) in enumerate(rows):
-        n = p.numel()
-        offsets.append(flat_off)
-        off = 0
-        while off < n:
-            ln = min(chunk, n - off)
-            chunk_rows.append((i, off, ln, flat_off + off))
-            off += ln
-        flat_off += -(-n // 4) * 4
+    chunk_rows, offsets, flat_off = _chunk_table(
+        [p.numel() for p, _ in rows], chunk, pad_to=4)    # quad-aligned slots
     assert flat_off == total
     dev = rows[0][0].device
     meta = (torch.tensor(ptr_rows, dtype=torch.int64, device=dev),
@@ -1119,21 +1145,17 @@ def compose_theta_bf16(ext, gw: torch.Tensor, atten: Optional[torch.Tensor],
     channels-last 4-D weights the physical index of that dim is
     (i / C) % kw.  `out`: a bf16 buffer in gw's layout to compose into."""
     gw_d = gw.detach()
-    if gw_d.dim() == 4 and gw_d.is_contiguous():
-        # NCHW-ordered 4-D weight: the last dim is physically last too
-        inner, L = 1, gw_d.shape[-1]
-    elif gw_d.dim() == 4:
-        assert gw_d.is_contiguous(memory_format=torch.channels_last)
-        inner, L = gw_d.shape[1], gw_d.shape[-1]
-    else:
-        assert gw_d.is_contiguous()
-        inner = 1
-        L = atten.numel() if atten is not None else 1
-    if atten is not None:
-        assert atten.numel() == L
+    L, inner = atten_geometry(gw_d)
+    if atten is not None and atten.numel() != L:
+        # a non-4-D weight may be the flattened view of one whose last dim
+        # atten spans (the 1×1 route's [K, C·1·1]): atten then tiles its rows
+        if gw_d.dim() == 4 or not atten.numel() or L % atten.numel():
+            raise ValueError(f"compose_theta_bf16: {atten.numel()} atten "
+                             f"entries do not fit a last weight dim of {L}")
+        L = atten.numel()
     if out is None:
         out = torch.empty_like(gw_d, dtype=torch.bfloat16)
-    elif out.dtype != torch.bfloat16 or not _same_layout(out, gw_d):
+    elif out.dtype != torch.bfloat16 or not same_layout(out, gw_d):
         raise ValueError("compose_theta_bf16: out must be bf16 in gw's layout")
     ext.compose2(gw_d.data_ptr(),
                  atten.detach().float().contiguous().data_ptr() if atten is not None else 0,
@@ -1465,45 +1487,23 @@ HEAD_STEP_CHUNK = 1 << 14
 _HS_GRAD_BF16, _HS_VEC, _HS_THETA, _HS_ATTEN_VEC = 1, 2, 4, 8
 
 
-def _same_layout(t: torch.Tensor, like: torch.Tensor) -> bool:
-    """Same shape and the same PHYSICAL layout: strides compared on every
-    dim of extent > 1 (a size-1 dim's stride is arbitrary)."""
-    return t.shape == like.shape and all(
-        a == b for a, b, n in zip(t.stride(), like.stride(), like.shape)
-        if n > 1)
-
-
 def head_step_partials(rows) -> int:
     """Number of drift partials a head_step over `rows` writes."""
     return sum(-(-r["aw"].numel() // HEAD_STEP_CHUNK) for r in rows)
-
-
-def _head_step_geometry(aw: torch.Tensor):
-    """(L, inner): atten broadcasts over the LOGICAL last dim, whose
-    physical index is (i / inner) % L — inner = C for channels-last
-    [K][kh][kw][C] storage, 1 when the last dim is also physically last."""
-    if aw.dim() < 1 or aw.numel() == 0:
-        raise ValueError("head_step: empty adaptive weight")
-    if aw.is_contiguous():
-        return aw.shape[-1], 1
-    if aw.dim() == 4 and aw.is_contiguous(memory_format=torch.channels_last):
-        return aw.shape[-1], aw.shape[1]
-    raise ValueError("head_step: adaptive weight is neither contiguous nor "
-                     f"channels-last dense (strides {aw.stride()})")
 
 
 def _head_step_row(r: Dict, partial0: int):
     aw = r["aw"]
     if not aw.is_cuda or aw.dtype != torch.float32:
         raise TypeError("head_step: aw must be a CUDA fp32 tensor")
-    L, inner = _head_step_geometry(aw)
+    L, inner = atten_geometry(aw)
     for k in ("aw0", "m", "v", "dw"):
         t = r.get(k)
         if t is None:
             raise ValueError(f"head_step: missing '{k}' (null pointer)")
         if not t.is_cuda or t.device != aw.device:
             raise TypeError(f"head_step: '{k}' is not on aw's device")
-        if t.numel() != aw.numel() or not _same_layout(t, aw):
+        if t.numel() != aw.numel() or not same_layout(t, aw):
             raise ValueError(
                 f"head_step: '{k}' {tuple(t.shape)}/{t.stride()} does not "
                 f"match aw's layout {tuple(aw.shape)}/{aw.stride()}")
@@ -1525,10 +1525,10 @@ def _head_step_row(r: Dict, partial0: int):
             raise ValueError("head_step: theta needs gw and atten "
                              "(null pointer)")
         if (gw.dtype != torch.float32 or gw.device != aw.device
-                or not _same_layout(gw, aw)):
+                or not same_layout(gw, aw)):
             raise ValueError("head_step: gw does not match aw's layout")
         if (theta.dtype != torch.bfloat16 or theta.device != aw.device
-                or not _same_layout(theta, aw)):
+                or not same_layout(theta, aw)):
             raise ValueError("head_step: theta must be bf16 in aw's layout")
         if (atten.dtype != torch.float32 or atten.device != aw.device
                 or not atten.is_contiguous() or atten.numel() != L):

@@ -19,6 +19,7 @@
 // k-groups: k = (lane>>4)*4 + e (e<4) and k = 16 + (lane>>4)*4 + (e-4).
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

@@ -31,6 +31,7 @@
 // (ref models the same torch module family: ref:models/resnet.py).
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

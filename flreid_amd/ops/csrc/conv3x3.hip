@@ -13,6 +13,7 @@
 // C % 32 == 0, K % 16 == 0.
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

@@ -34,6 +34,7 @@
 // at the staging loads.
 
 #include "common.h"
+#include "ops.h"
 
 #include <algorithm>
 

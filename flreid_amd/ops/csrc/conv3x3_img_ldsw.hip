@@ -19,6 +19,7 @@
 //    zero at the LDS store (branching around loads serialises them).
 
 #include "common.h"
+#include "ops.h"
 
 #include <algorithm>
 

@@ -49,6 +49,7 @@
 // loop (the backward in passes of 8 accumulators).
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

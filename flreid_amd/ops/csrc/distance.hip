@@ -17,6 +17,7 @@
 // sub-tile, LDS-staged K panels (BK=32, padded rows: conflict-free b32 reads).
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

@@ -16,6 +16,7 @@
 // one 64 K-element chunk per workgroup.
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

@@ -15,6 +15,7 @@
 // All kernels: fp32 compute; bf16 or fp32 I/O.
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

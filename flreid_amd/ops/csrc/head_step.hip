@@ -30,6 +30,7 @@
 // partials is then the correctly rounded drift, whatever the chunking.
 
 #include "common.h"
+#include "ops.h"
 
 #include <vector>
 
@@ -238,10 +239,10 @@ __global__ __launch_bounds__(HS_BLOCK) void head_step_kernel(
 
 extern "C" int flreid_head_step_chunk() { return HS_CHUNK; }
 
-// rows: n × 14 int64 — aw, aw0, dw, gw, atten, m, v, theta, step (device
-// addresses), numel, L, inner, flags, partial0.  Validates every row, then
-// launches (several launches when the table exceeds the argument limit).
-// Throws before the first launch on any violated check.
+// rows: n × kHeadStepFields (ops.h) int64 — aw, aw0, dw, gw, atten, m, v,
+// theta, step (device addresses), numel, L, inner, flags, partial0.
+// Validates every row, then launches (several launches when the table
+// exceeds the argument limit).  Throws before the first launch on any violated check.
 extern "C" void flreid_head_step(const int64_t* rows, int n_rows,
                                  double* partials, int64_t n_partials,
                                  double lr, double beta1, double beta2,
@@ -250,7 +251,7 @@ extern "C" void flreid_head_step(const int64_t* rows, int n_rows,
   if (n_rows <= 0) throw std::runtime_error("head_step: empty tensor table");
   if (!partials) throw std::runtime_error("head_step: null partials");
   for (int r = 0; r < n_rows; ++r) {
-    const int64_t* row = rows + (int64_t)r * 14;
+    const int64_t* row = rows + (int64_t)r * kHeadStepFields;
     const int flags = (int)row[12];
     const bool th = flags & kHsTheta;
     const int64_t numel = row[9], L = row[10], inner = row[11];
@@ -291,7 +292,7 @@ extern "C" void flreid_head_step(const int64_t* rows, int n_rows,
     HeadStepArgs args;
     int n = 0, blocks = 0;
     for (; r < n_rows && n < HS_MAX_TENSORS; ++r, ++n) {
-      const int64_t* row = rows + (int64_t)r * 14;
+      const int64_t* row = rows + (int64_t)r * kHeadStepFields;
       HeadStepTensor& t = args.t[n];
       t.aw = reinterpret_cast<float*>(row[0]);
       t.aw0 = reinterpret_cast<const float*>(row[1]);

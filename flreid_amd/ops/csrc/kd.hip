@@ -23,6 +23,7 @@
 // are head outputs) — fp32 here is bit-comparable with the eager reference.
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

@@ -16,6 +16,7 @@
 // wrapper).
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

@@ -32,6 +32,7 @@
 // wrapper's eligibility test), so the float4 body never straddles.
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

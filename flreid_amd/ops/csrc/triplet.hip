@@ -14,6 +14,7 @@
 // fp32 features (the training path normalises/loss in fp32).
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

@@ -15,6 +15,7 @@
 // Grid = BW·H workgroups ≫ 256 CUs at Swin shapes (stage 1 tiny: 12k).
 
 #include "common.h"
+#include "ops.h"
 
 namespace flreid {
 

@@ -475,6 +475,57 @@ def test_l1_drift_fused_matches_foreach():
     assert torch.allclose(loss2, ref_loss, rtol=1e-6)
 
 
+def test_l1_drift_eligibility_and_anchor_lifetime():
+    """The fused drift path needs 16-byte aligned pairs (its forward reads
+    float4): a misaligned pair sends the whole call to the reference, and the
+    autograd node keeps the anchors its table points to alive."""
+    torch.manual_seed(5)
+    sizes = [5, 4, (1 << 16) + 3]    # the last: two chunks and a scalar tail
+    values = [torch.randn(n, device="cuda") for n in sizes]
+    anchors = [torch.randn(n, device="cuda") for n in sizes]
+
+    def leaves(misalign_first=False):
+        ps = [v.clone() for v in values]
+        if misalign_first:
+            buf = torch.empty(sizes[0] + 1, device="cuda")
+            buf[1:].copy_(values[0])
+            ps[0] = buf[1:]
+        return [p.requires_grad_(True) for p in ps]
+
+    p_ref = leaves()
+    ref_loss = ref.l1_drift_fused(list(zip(p_ref, anchors)))
+    ref_loss.backward()
+
+    def check(loss, params, fused=True):
+        assert ("L1DriftHipFn" in type(loss.grad_fn).__name__) == fused
+        assert torch.allclose(loss, ref_loss, rtol=1e-6)
+        loss.backward()
+        for p, q in zip(params, p_ref):
+            assert torch.equal(p.grad, q.grad)
+
+    # 1. allocator-aligned pairs: the fused kernels
+    params = leaves()
+    assert all(p.data_ptr() % 16 == 0 for p in params)
+    check(ops.l1_drift(list(zip(params, anchors))), params)
+
+    # 2. the first p starts one float into its buffer: the reference runs
+    params = leaves(misalign_first=True)
+    assert params[0].data_ptr() % 16 == 4 and params[0].is_leaf
+    n_meta = len(ops._DRIFT_META)
+    check(ops.l1_drift(list(zip(params, anchors))), params, fused=False)
+    assert len(ops._DRIFT_META) == n_meta
+
+    # 3. the caller drops its anchors between forward and backward; fresh
+    # allocations of the same sizes would reuse freed anchor memory
+    params = leaves()
+    mine = [a.clone() for a in anchors]
+    loss = ops.l1_drift(list(zip(params, mine)))
+    del mine
+    junk = [torch.full((n,), float("nan"), device="cuda") for n in sizes]
+    check(loss, params)
+    del junk
+
+
 def test_adaptive_conv1x1_fused_route(monkeypatch):
     """Default-on fused pointwise route (compose2-to-bf16 + bf16 hipBLASLt,
     _AdaptiveLinear1x1Fn) vs the eager compose+linear fallback."""
