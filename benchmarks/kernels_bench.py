@@ -115,7 +115,7 @@ def bench_head_step(results, n):
 
     opt = torch.optim.Adam(params, lr=1e-3, weight_decay=1e-5, fused=True,
                            capturable=True)
-    ext = ops._ext_or_raise("compose2")
+    ext = ops.require_extension("compose2")
     pairs = list(zip(params, anchors))
 
     def unfused():
@@ -137,7 +137,7 @@ def bench_head_step(results, n):
     cls = rows[-1]
     with torch.no_grad():
         results["classifier_fwd_k2_theta"] = bench(
-            lambda: ops.theta_linear(x, cls["theta"], None, k2=True), n)
+            lambda: ops.adaptive_linear(x, cls["theta"], None, None, None), n)
         results["classifier_fwd_k2_compose"] = bench(
             lambda: ops.adaptive_linear_fwd(x, cls["gw"], cls["atten"],
                                             cls["aw"], None), n)

@@ -9,6 +9,7 @@ distinctive pieces (penalties, state schemas, aggregation).
 from __future__ import annotations
 
 import collections
+import contextlib
 import os
 from typing import Any, Dict, List, Optional, Union
 
@@ -121,8 +122,6 @@ class FusedHeadStep:
 
     def live_theta(self):
         """Context manager for one head epoch's live θ (no-op when off)."""
-        import contextlib
-
         from flreid_amd.models.adaptive import live_theta_scope
         if not self.live:
             return contextlib.nullcontext()

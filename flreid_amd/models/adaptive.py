@@ -14,10 +14,12 @@ the composed weight right after dispatch equals the dispatched global weight
 `initial_*` snapshots anchor the round's L1 drift regulariser
 (ref:methods/fedstil.py:639-644).
 
-On GPU the composition runs through the fused HIP compose kernel
+On GPU the composition runs through the fused HIP compose2 kernel
 (flreid_amd.ops.adaptive_compose) so θ is produced in one pass; the backward
 for adaptive_weight is identity and atten (when learnable) reduces over all
-dims but the last.
+dims but the last.  The Linear and Conv2d forwards only name the layer's
+shape; which kernels run is decided in ops.conv3x3_try and
+ops.adaptive_linear alone.
 """
 
 from __future__ import annotations
@@ -160,6 +162,15 @@ class AdaptiveBase(nn.Module):
         return ops.adaptive_compose(self.global_weight, self.global_weight_atten,
                                     self.adaptive_weight)
 
+    def _weights(self):
+        """(weight, atten, aw) as the ops routes take them: the live bf16 θ
+        with (None, None) during a head epoch — read, not composed — else
+        the decomposed parameters."""
+        if self._live is not None:
+            return self._live(self.adaptive_weight), None, None
+        return (self.global_weight, self.global_weight_atten,
+                self.adaptive_weight)
+
     def drift_pairs(self):
         """(current, round-start) pairs for the L1 drift regulariser."""
         return [(self.global_weight_atten, self.initial_global_weight_atten),
@@ -168,27 +179,14 @@ class AdaptiveBase(nn.Module):
 
 class AdaptiveLinear(AdaptiveBase):
     def forward(self, data: torch.Tensor) -> torch.Tensor:
-        if self._live is not None:
-            # head epoch: θ is read from the live buffer, not composed
-            theta = self._live(self.adaptive_weight)
-            # forward GEMM: the K2 tile loop on the ready θ by default — it
-            # sums in the composing K2 kernel's order, so the round stays
-            # bit-identical to the unfused path.  FLREID_CLASSIFIER_GEMM=lib
-            # takes hipBLASLt instead (faster at 64×8000×2048, other
-            # summation order — profiles/README.md)
-            k2 = os.environ.get("FLREID_CLASSIFIER_GEMM", "k2") != "lib"
-            y = ops.theta_linear(data, theta, self.adaptive_bias, k2=k2) \
-                if data.dim() == 2 else None
-            return y if y is not None else F.linear(data, theta,
-                                                    self.adaptive_bias)
-        if data.dim() == 2:
-            # fused MFMA GEMM with compose-in-prologue (K2); falls back to
-            # compose + F.linear off-GPU or when atten trains
-            return ops.adaptive_linear(data, self.global_weight,
-                                       self.global_weight_atten,
-                                       self.adaptive_weight,
-                                       self.adaptive_bias)
-        return F.linear(data, self.composed_weight(), self.adaptive_bias)
+        weight, atten, aw = self._weights()
+        # the K2 GEMM (compose-in-prologue, or the tile loop on the live θ);
+        # None off-GPU, for 3-D input or when atten trains
+        y = ops.adaptive_linear(data, weight, atten, aw, self.adaptive_bias)
+        if y is not None:
+            return y
+        theta = weight if atten is None else self.composed_weight()
+        return F.linear(data, theta, self.adaptive_bias)
 
 
 def _is_one(v) -> bool:
@@ -205,66 +203,37 @@ class AdaptiveConv2d(AdaptiveBase):
         self.stride = stride
         self.padding = padding
 
-    def _forward_live(self, data: torch.Tensor) -> torch.Tensor:
-        """Head-epoch forward on the live bf16 θ — the routes of forward()
-        without their compose and gradient-cast passes."""
-        theta = self._live(self.adaptive_weight)
-        k = theta.shape
-        if (k[2] == 3 and k[3] == 3 and _is_one(self.stride)
-                and _is_one(self.padding) and self.adaptive_bias is None):
-            y = ops.conv3x3_try(data, theta)
+    def forward(self, data: torch.Tensor) -> torch.Tensor:
+        weight, atten, aw = self._weights()
+        bias = self.adaptive_bias
+        k, c, kh, kw = weight.shape
+        if ((kh, kw) == (3, 3) and _is_one(self.stride)
+                and _is_one(self.padding) and bias is None):
+            # K1: θ composed to bf16 in one pass (or the live θ as it is),
+            # then the hand-written or the library conv by ops' policy
+            y = ops.conv3x3_try(data, weight, atten, aw)
             if y is not None:
                 return y
-        if (k[2] == 1 and k[3] == 1 and _is_one(self.stride)
-                and _is_zero(self.padding)
-                and os.environ.get("FLREID_NO_FUSED_1X1", "0") != "1"):
-            b, c, h, w = data.shape
+        if ((kh, kw) == (1, 1) and _is_one(self.stride)
+                and _is_zero(self.padding) and data.is_cuda):
+            # pointwise conv == GEMM over N·H·W; on channels-last input the
+            # [NHW, C] view is free.  Default route: compose2 to bf16 + bf16
+            # library GEMMs fwd/bwd (FLREID_NO_FUSED_1X1=1 disables it)
+            b, _, h, w = data.shape
             xv = data.permute(0, 2, 3, 1).reshape(-1, c)
-            y = ops.theta_linear(xv, theta.view(k[0], c), self.adaptive_bias)
+            y = ops.adaptive_linear(
+                xv, weight.view(k, c), atten,
+                aw.view(k, c) if aw is not None and aw.numel() else None,
+                bias, engine="lib")
+            if y is None and atten is not None:
+                # the composed fallback stays a GEMM on the view; the live
+                # one below is the conv (other library call, other bits)
+                y = F.linear(xv, self.composed_weight().view(k, c), bias)
             if y is not None:
                 return y.view(b, h, w, -1).permute(0, 3, 1, 2)
-        return F.conv2d(data, theta, self.adaptive_bias,
-                        stride=self.stride, padding=self.padding)
-
-    def forward(self, data: torch.Tensor) -> torch.Tensor:
-        if self._live is not None and self.global_weight.dim() == 4:
-            return self._forward_live(data)
-        gw = self.global_weight
-        if (data.is_cuda and gw.dim() == 4 and gw.shape[2] == 3
-                and gw.shape[3] == 3 and _is_one(self.stride)
-                and _is_one(self.padding) and self.adaptive_bias is None
-                and not gw.requires_grad
-                and not self.global_weight_atten.requires_grad):
-            # hand-written K1 conv (conv3x3_img.hip): θ composed to bf16 in
-            # the weight fetch, halo-staged MFMA fwd + dgrad/wgrad kernels
-            y = ops.conv3x3_try(data, gw, self.global_weight_atten,
-                                self.adaptive_weight)
-            if y is not None:
-                return y
-        if (data.is_cuda and gw.dim() == 4 and gw.shape[2] == 1
-                and gw.shape[3] == 1 and _is_one(self.stride)
-                and _is_zero(self.padding)):
-            # pointwise conv == GEMM over N·H·W; on channels-last input the
-            # [NHW, C] view is free.  DEFAULT route (K2): θ composed
-            # straight to bf16 (compose2 — one pass, no fp32 θ, no autocast
-            # cast) + bf16 hipBLASLt GEMMs fwd/bwd, aw's grad cast once to
-            # fp32.  Disable with FLREID_NO_FUSED_1X1=1.
-            b, c, h, w = data.shape
-            n_out = gw.shape[0]
-            xv = data.permute(0, 2, 3, 1).reshape(-1, c)
-            y = None
-            if not gw.requires_grad and not self.global_weight_atten.requires_grad:
-                aw2d = self.adaptive_weight.view(n_out, c) \
-                    if self.adaptive_weight.numel() else None
-                y = ops.adaptive_linear_1x1(xv, gw.view(n_out, c),
-                                            self.global_weight_atten, aw2d,
-                                            self.adaptive_bias)
-            if y is None:
-                theta = self.composed_weight().view(n_out, c)
-                y = F.linear(xv, theta, self.adaptive_bias)
-            return y.view(b, h, w, -1).permute(0, 3, 1, 2)
-        return F.conv2d(data, self.composed_weight(), self.adaptive_bias,
-                        stride=self.stride, padding=self.padding)
+        theta = weight if atten is None else self.composed_weight()
+        return F.conv2d(data, theta, bias, stride=self.stride,
+                        padding=self.padding)
 
 
 class AdaptiveBatchNorm2d(AdaptiveBase):

@@ -131,10 +131,9 @@ def _chunk_table(numels: Sequence[int], chunk: int, pad_to: int = 1):
     return chunk_rows, offsets, flat_off
 
 
-# the names these had before they had callers outside ops/
+# the name require_extension had before it had callers outside ops/; test
+# files written against it keep running
 _ext_or_raise = require_extension
-_same_layout = same_layout
-_head_step_geometry = atten_geometry
 
 
 # ---------------------------------------------------------------------------
@@ -161,7 +160,7 @@ def _pairwise_gpu(ext, a: torch.Tensor, b: torch.Tensor, mode: int) -> torch.Ten
 def similarity_matrix(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """A·Bᵀ — the eval GEMM."""
     if a.is_cuda and not a.requires_grad and not b.requires_grad:
-        ext = _ext_or_raise("pairwise")
+        ext = require_extension("pairwise")
         if ext is not None:
             return _pairwise_gpu(ext, a, b, 0)
     return a.float() @ b.float().t()
@@ -169,7 +168,7 @@ def similarity_matrix(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 def pairwise_sqeuclidean(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     if a.is_cuda and not a.requires_grad and not b.requires_grad:
-        ext = _ext_or_raise("pairwise")
+        ext = require_extension("pairwise")
         if ext is not None:
             return _pairwise_gpu(ext, a, b, 2)
     return ref.pairwise_sqeuclidean(a, b)
@@ -177,7 +176,7 @@ def pairwise_sqeuclidean(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 def pairwise_cosine_distance(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     if a.is_cuda and not a.requires_grad and not b.requires_grad:
-        ext = _ext_or_raise("pairwise")
+        ext = require_extension("pairwise")
         if ext is not None:
             return _pairwise_gpu(ext, l2_normalize(a.float()),
                                  l2_normalize(b.float()), 1)
@@ -191,7 +190,7 @@ def pairwise_cosine_distance(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 def l2_normalize(x: torch.Tensor, dim: int = 1) -> torch.Tensor:
     if (x.is_cuda and x.dim() == 2 and dim in (1, -1)
             and not x.requires_grad and x.dtype in (torch.float32, torch.bfloat16)):
-        ext = _ext_or_raise("l2norm_rows")
+        ext = require_extension("l2norm_rows")
         if ext is not None:
             x = x.contiguous()
             y = torch.empty_like(x)
@@ -227,7 +226,7 @@ class _CeLabelSmoothFn(torch.autograd.Function):
 def ce_label_smooth(score: torch.Tensor, target: torch.Tensor,
                     epsilon: float = 0.1) -> torch.Tensor:
     if score.is_cuda and score.dim() == 2:
-        ext = _ext_or_raise("ce_smooth")
+        ext = require_extension("ce_smooth")
         if ext is not None:
             return _CeLabelSmoothFn.apply(score, target.long(), epsilon, ext)
     return ref.ce_label_smooth(score, target, epsilon)
@@ -247,9 +246,9 @@ class _ComposeFn(torch.autograd.Function):
         gw_c, aw_c = gw.contiguous(), aw.contiguous()
         at = atten.detach().contiguous().float()
         out = torch.empty_like(gw_c)
-        ext.compose(gw_c.data_ptr(), at.data_ptr(), aw_c.data_ptr(),
-                    out.data_ptr(), gw_c.numel(), gw_c.shape[-1], _dt(gw_c),
-                    _stream())
+        ext.compose2(gw_c.data_ptr(), at.data_ptr(), aw_c.data_ptr(),
+                     out.data_ptr(), gw_c.numel(), gw_c.shape[-1], 1,
+                     _dt(gw_c), _dt(gw_c), _stream())
         ctx.atten_requires = atten.requires_grad
         if ctx.atten_requires:
             ctx.save_for_backward(gw_c)
@@ -269,7 +268,7 @@ def adaptive_compose(global_weight: torch.Tensor, atten: torch.Tensor,
     if (global_weight.is_cuda and not global_weight.requires_grad
             and global_weight.dtype in (torch.float32, torch.bfloat16)
             and adaptive_weight.dtype == global_weight.dtype):
-        ext = _ext_or_raise("compose")
+        ext = require_extension("compose2")
         if ext is not None:
             return _ComposeFn.apply(global_weight, atten, adaptive_weight, ext)
     return ref.adaptive_compose(global_weight, atten, adaptive_weight)
@@ -379,7 +378,7 @@ def decomposed_compose(sw: torch.Tensor, mask: torch.Tensor, aw: torch.Tensor,
             and mask.numel() == sw.shape[0] and mask.is_contiguous()):
         geom = _decomposed_geometry(sw)
         if geom is not None and geom == _decomposed_geometry(aw):
-            ext = _ext_or_raise("decomposed_fwd")
+            ext = require_extension("decomposed_fwd")
             if ext is not None:
                 return _DecomposedComposeFn.apply(
                     sw, mask, aw, aw_kb, atten, lambda_l1, lambda_mask,
@@ -400,7 +399,7 @@ def importance_update(importance: Dict[str, torch.Tensor],
                       scale: float = 1.0) -> None:
     first = next(iter(importance.values()), None)
     if first is not None and first.is_cuda:
-        ext = _ext_or_raise("importance")
+        ext = require_extension("importance")
         if ext is not None:
             for n, g in grads.items():
                 if g is None:
@@ -453,7 +452,7 @@ class _KdLossFn(torch.autograd.Function):
 def kd_loss(logits_student: torch.Tensor, logits_teacher: torch.Tensor,
             temperature: float = 4.0) -> torch.Tensor:
     if logits_student.is_cuda and logits_student.dim() == 2:
-        ext = _ext_or_raise("kd_fwd")
+        ext = require_extension("kd_fwd")
         if ext is not None:
             return _KdLossFn.apply(logits_student, logits_teacher,
                                    temperature, ext)
@@ -494,7 +493,7 @@ def icarl_distill_loss(score: torch.Tensor, target: torch.Tensor,
     sigmoid(prev_logits)) — fused on GPU, eager reference elsewhere."""
     if (score.is_cuda and score.dim() == 2
             and prev_logits.shape[1] <= score.shape[1]):
-        ext = _ext_or_raise("icarl_distill")
+        ext = require_extension("icarl_distill")
         if ext is not None:
             return _IcarlDistillFn.apply(score, target, prev_logits, ext)
     return ref.icarl_distill_loss(score, target, prev_logits)
@@ -538,7 +537,7 @@ def triplet_loss(feature: torch.Tensor, target: torch.Tensor,
                  hard_mining: bool = True) -> torch.Tensor:
     if (feature.is_cuda and hard_mining and not norm_feat
             and margin is not None and margin > 0 and feature.dim() == 2):
-        ext = _ext_or_raise("triplet_fwd")
+        ext = require_extension("triplet_fwd")
         if ext is not None:
             return _TripletHardFn.apply(feature.float(), target.long(),
                                         margin, ext)
@@ -602,7 +601,7 @@ class _WindowAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, bias, mask, scale):
-        ext = _ext_or_raise("window_attn_fwd")
+        ext = require_extension("window_attn_fwd")
         out, qc, kc, vc, bias_c, mask_c = _window_attn_fwd_raw(
             ext, q.detach(), k.detach(), v.detach(), bias, mask, scale)
         ctx.save_for_backward(qc, kc, vc, bias_c)
@@ -613,7 +612,7 @@ class _WindowAttnFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        ext = _ext_or_raise("window_attn_bwd")
+        ext = require_extension("window_attn_bwd")
         qc, kc, vc, bias_c = ctx.saved_tensors
         mask_c = ctx.mask_c
         bw, h, n, d = qc.shape
@@ -643,7 +642,7 @@ def window_attention(q, k, v, bias, mask, scale, dropout=None):
     if (q.is_cuda and q.shape[-2] <= 64 and q.shape[-1] <= 64
             and drop_p == 0.0 and extension_available()):
         if not torch.is_grad_enabled():
-            ext = _ext_or_raise("window_attn_fwd")
+            ext = require_extension("window_attn_fwd")
             out, *_ = _window_attn_fwd_raw(ext, q, k, v, bias, mask, scale)
             return out
         return _WindowAttnFn.apply(q, k, v, bias, mask, scale)
@@ -658,7 +657,7 @@ class _PatchMergeLNFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, H, W, eps):
-        ext = _ext_or_raise("patch_merge_ln_fwd")
+        ext = require_extension("patch_merge_ln_fwd")
         x_c = x.detach().contiguous()
         b, L, c = x_c.shape
         rows = b * (H // 2) * (W // 2)
@@ -677,7 +676,7 @@ class _PatchMergeLNFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        ext = _ext_or_raise("patch_merge_ln_bwd")
+        ext = require_extension("patch_merge_ln_bwd")
         x_c, gamma_c, mean, rstd = ctx.saved_tensors
         H, W = ctx.hw
         b, L, c = x_c.shape
@@ -721,7 +720,7 @@ def adaptive_linear_fwd(x: torch.Tensor, gw: torch.Tensor,
 
     x bf16 [M, K]; gw/aw fp32 [N, K]; atten fp32 [K]; bias fp32 [N].
     """
-    ext = _ext_or_raise("adaptive_linear_fwd")
+    ext = require_extension("adaptive_linear_fwd")
     if ext is None:
         theta = ref.adaptive_compose(gw, atten, aw) if atten is not None else gw
         return (torch.nn.functional.linear(x.float(), theta,
@@ -737,50 +736,6 @@ def adaptive_linear_fwd(x: torch.Tensor, gw: torch.Tensor,
         bias.contiguous().float().data_ptr() if bias is not None else 0,
         out.data_ptr(), m, n, k, split_layout, _stream())
     return out
-
-
-class _AdaptiveLinearFn(torch.autograd.Function):
-    """Autograd wrapper for the fused K2 GEMM: fwd composes θ in the weight
-    fetch; bwd materialises θ once (compose kernel) for grad_x and computes
-    grad_aw = gᵀ·x.  atten/gw are frozen in FedSTIL (no grads)."""
-
-    @staticmethod
-    def forward(ctx, x, gw, atten, aw, bias):
-        x_bf = x.detach().to(torch.bfloat16).contiguous()
-        out = adaptive_linear_fwd(x_bf, gw.detach(), atten, aw.detach(),
-                                  bias.detach() if bias is not None else None)
-        ctx.save_for_backward(x_bf, gw, atten, aw)
-        ctx.has_bias = bias is not None
-        ctx.x_dtype = x.dtype
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        x_bf, gw, atten, aw = ctx.saved_tensors
-        g = grad_out.to(torch.bfloat16)
-        ext = _load_extension()
-        if ext is not None and gw.dtype == torch.float32:
-            theta = compose_theta_bf16(ext, gw.contiguous(), atten,
-                                       aw.contiguous())
-        else:
-            theta = adaptive_compose(gw, atten, aw).to(torch.bfloat16)
-        grad_x = (g @ theta).to(ctx.x_dtype)
-        grad_aw = (g.t() @ x_bf).to(aw.dtype)
-        grad_bias = grad_out.sum(0).to(torch.float32) if ctx.has_bias else None
-        return grad_x, None, None, grad_aw, grad_bias
-
-
-def adaptive_linear(x: torch.Tensor, gw: torch.Tensor, atten: torch.Tensor,
-                    aw: torch.Tensor, bias: Optional[torch.Tensor]):
-    """Adaptive linear layer forward: fused MFMA path on GPU (frozen
-    gw/atten), eager compose+linear elsewhere."""
-    if (x.is_cuda and x.dim() == 2 and not gw.requires_grad
-            and not atten.requires_grad and gw.shape[-1] % 32 == 0
-            and atten.numel() == gw.shape[-1]      # kernel contract: atten[K]
-            and extension_available()):
-        return _AdaptiveLinearFn.apply(x, gw, atten, aw, bias)
-    theta = adaptive_compose(gw, atten, aw)
-    return torch.nn.functional.linear(x, theta, bias)
 
 
 def bn_eval_2d(x: torch.Tensor, bn, relu: bool = False) -> Optional[torch.Tensor]:
@@ -826,7 +781,7 @@ class _L1DriftHipFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, meta, *tensors):        # tensors: the params, the anchors
-        ext = _ext_or_raise("drift")
+        ext = require_extension("drift")
         ptrs, chunks, sizes, total = meta
         partials = torch.empty(chunks.shape[0], device=tensors[0].device,
                                dtype=torch.float32)
@@ -839,7 +794,7 @@ class _L1DriftHipFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        ext = _ext_or_raise("drift")
+        ext = require_extension("drift")
         ptrs, chunks, sizes, total = ctx.meta
         flat = torch.empty(total, device=grad_out.device, dtype=torch.float32)
         g = grad_out.to(torch.float32).contiguous()
@@ -956,7 +911,7 @@ class _QuadraticPenaltyHipFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, meta, consts, *params):
-        ext = _ext_or_raise("penalty_fwd")
+        ext = require_extension("penalty_fwd")
         ptrs, chunks, n_sets, offsets, total = meta
         partials = torch.empty(chunks.shape[0], device=params[0].device,
                                dtype=torch.float32)
@@ -971,7 +926,7 @@ class _QuadraticPenaltyHipFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        ext = _ext_or_raise("penalty_bwd")
+        ext = require_extension("penalty_bwd")
         params = ctx.saved_tensors
         ptrs, chunks, n_sets, offsets, total = ctx.meta
         g = grad_out.to(torch.float32).contiguous()
@@ -1005,7 +960,7 @@ def quadratic_penalty_sets(
             and os.environ.get("FLREID_NO_FUSED_PENALTY", "0") != "1"):
         plan = _penalty_plan(params, sets)
         if plan is not None:
-            ext = _ext_or_raise("penalty_fwd")
+            ext = require_extension("penalty_fwd")
             if ext is not None:
                 rows, total = plan
                 meta = _penalty_meta(rows, len(sets), total,
@@ -1036,7 +991,7 @@ class _BnTrain2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps,
                 nbt, relu):
-        ext = _ext_or_raise("bn_train")
+        ext = require_extension("bn_train")
         c = x.shape[1]
         m = x.numel() // c
         y = torch.empty_like(x)
@@ -1072,7 +1027,7 @@ class _BnTrain2dFn(torch.autograd.Function):
             dy = dy.contiguous()
         if dy.dtype != x.dtype:
             dy = dy.to(x.dtype)
-        ext = _ext_or_raise("bn_train")
+        ext = require_extension("bn_train")
         c = x.shape[1]
         m = x.numel() // c
         dx = torch.empty_like(x)
@@ -1165,106 +1120,115 @@ def compose_theta_bf16(ext, gw: torch.Tensor, atten: Optional[torch.Tensor],
     return out
 
 
-class _AdaptiveLinear1x1Fn(torch.autograd.Function):
-    """Default-on fused adaptive 1×1/linear path (K2 at M=N·H·W): θ is
-    composed straight to bf16 (compose2 — no fp32 θ in HBM, no autocast
-    cast pass) and the GEMMs run bf16 hipBLASLt.  aw's gradient is the
-    bf16 wgrad GEMM cast once to fp32.  gw/atten frozen (FedSTIL)."""
+class _AdaptiveLinearFn(torch.autograd.Function):
+    """y = x·θᵀ + bias for the adaptive linear / 1×1 layers, in
+    _Conv3x3Fn's convention: θ = atten⊙weight + aw, or `weight` itself when
+    it is a ready bf16 θ (the head epoch's live θ; atten and aw None).
+
+    fwd:  k2  = the K2 tile loop: θ composed in its weight fetch and never
+                materialised, or loaded as it is when ready — the two sum in
+                the same order, so they agree bit for bit;
+          lib = θ composed straight to bf16 (compose2 — no fp32 θ in HBM,
+                no autocast cast pass) unless ready, then the bf16 library
+                GEMM.
+    bwd:  dx = g·θ (θ recomposed when the forward never materialised it),
+          dθ = gᵀ·x_bf, d_bias = Σg.  dθ IS d(aw) (identity composition),
+          cast once to fp32; a ready θ takes it in bf16 — no cast pass.
+    Only frozen weight/atten are supported next to aw (FedSTIL)."""
 
     @staticmethod
-    def forward(ctx, x, gw2d, atten, aw2d, bias):
-        ext = _ext_or_raise("compose2")
+    def forward(ctx, x, weight, atten, aw, bias, engine):
+        ext = require_extension("adaptive_linear")
         x_bf = x.detach().to(torch.bfloat16).contiguous()
-        theta = compose_theta_bf16(ext, gw2d, atten, aw2d)
-        y = x_bf @ theta.t()
-        if bias is not None:
-            y = y + bias.detach().to(torch.bfloat16)
-        ctx.save_for_backward(x_bf, theta)
-        ctx.x_dtype = x.dtype
-        ctx.has_bias = bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        x_bf, theta = ctx.saved_tensors
-        g = grad_out.to(torch.bfloat16)
-        dx = (g @ theta).to(ctx.x_dtype)
-        d_aw = (g.t() @ x_bf).to(torch.float32)
-        d_bias = grad_out.sum(0).to(torch.float32) if ctx.has_bias else None
-        return dx, None, None, d_aw, d_bias
-
-
-class _ThetaLinearFn(torch.autograd.Function):
-    """y = x·θᵀ + bias on a ready bf16 θ (the head epoch's live θ): the same
-    GEMMs as _AdaptiveLinearFn / _AdaptiveLinear1x1Fn without their compose
-    and cast passes — θ is read as it is and its gradient leaves in bf16.
-    k2: forward on the K2 tile loop with the bf16-load prologue
-    (bit-identical to the composing K2 kernel); else hipBLASLt."""
-
-    @staticmethod
-    def forward(ctx, x, theta, bias, k2):
-        x_bf = x.detach().to(torch.bfloat16).contiguous()
-        th = theta.detach()
-        if k2:
-            ext = _ext_or_raise("theta_linear_fwd")
+        ready = weight.dtype == torch.bfloat16 and atten is None and aw is None
+        theta = weight.detach() if ready else None
+        if engine == "k2" and not ready:
+            y = adaptive_linear_fwd(x_bf, weight.detach(), atten, aw.detach(),
+                                    bias.detach() if bias is not None else None)
+        elif engine == "k2":
             m, k = x_bf.shape
-            n = th.shape[0]
-            y = torch.empty(m, n, device=x.device, dtype=torch.bfloat16)
+            y = torch.empty(m, theta.shape[0], device=x.device,
+                            dtype=torch.bfloat16)
             ext.theta_linear_fwd(
-                x_bf.data_ptr(), th.data_ptr(),
+                x_bf.data_ptr(), theta.data_ptr(),
                 bias.detach().contiguous().float().data_ptr()
                 if bias is not None else 0,
-                y.data_ptr(), m, n, k, _stream())
+                y.data_ptr(), m, theta.shape[0], k, _stream())
         else:
-            y = x_bf @ th.t()
+            if theta is None:
+                theta = compose_theta_bf16(ext, weight, atten, aw)
+            y = x_bf @ theta.t()
             if bias is not None:
                 y = y + bias.detach().to(torch.bfloat16)
-        ctx.save_for_backward(x_bf, th)
+        ctx.save_for_backward(x_bf, weight, atten, aw, theta)
         ctx.x_dtype = x.dtype
+        ctx.ready = ready
         ctx.has_bias = bias is not None
         return y
 
     @staticmethod
     def backward(ctx, grad_out):
-        x_bf, th = ctx.saved_tensors
+        x_bf, weight, atten, aw, theta = ctx.saved_tensors
         g = grad_out.to(torch.bfloat16)
-        dx = (g @ th).to(ctx.x_dtype) if ctx.needs_input_grad[0] else None
+        dx = None
+        if ctx.needs_input_grad[0]:
+            if theta is None:
+                theta = compose_theta_bf16(require_extension("compose2"),
+                                           weight.contiguous(), atten,
+                                           aw.contiguous())
+            dx = (g @ theta).to(ctx.x_dtype)
         d_theta = g.t() @ x_bf
+        d_weight = d_aw = None
+        if ctx.ready:
+            d_weight = d_theta
+        elif aw is not None:
+            d_aw = d_theta.to(torch.float32)
         d_bias = grad_out.sum(0).to(torch.float32) if ctx.has_bias else None
-        return dx, d_theta, d_bias, None
+        return dx, d_weight, None, d_aw, d_bias, None
 
 
-def theta_linear(x2d: torch.Tensor, theta2d: torch.Tensor,
-                 bias: Optional[torch.Tensor],
-                 k2: bool = False) -> Optional[torch.Tensor]:
-    """Linear layer on a ready bf16 θ [N, K]; None when out of regime (the
-    caller runs F.linear on θ)."""
-    if (not x2d.is_cuda or x2d.dim() != 2 or not extension_available()
-            or theta2d.dtype != torch.bfloat16
-            or not theta2d.is_contiguous()):
-        return None
-    if x2d.dtype != torch.bfloat16 and not torch.is_autocast_enabled():
-        return None
-    return _ThetaLinearFn.apply(x2d, theta2d, bias,
-                                bool(k2) and theta2d.shape[1] % 32 == 0)
+def adaptive_linear(x2d: torch.Tensor, weight: torch.Tensor,
+                    atten: Optional[torch.Tensor], aw: Optional[torch.Tensor],
+                    bias: Optional[torch.Tensor],
+                    engine: str = "k2") -> Optional[torch.Tensor]:
+    """The one dispatch guard of the adaptive linear / 1×1 routes: bf16
+    y = x2d·θᵀ + bias through _AdaptiveLinearFn, or None when out of regime
+    (the caller runs the library on θ).  θ = atten⊙weight + aw with frozen
+    fp32 weight/atten, or `weight` itself: a ready, contiguous bf16 [N, K] θ
+    with atten and aw None.
 
+    engine "k2" is the classifier's route, the K2 tile loop.  Composing, it
+    needs K % 32 == 0 and one atten entry per column; a ready θ goes to the
+    library GEMM instead when K % 32 != 0 or FLREID_CLASSIFIER_GEMM=lib
+    (faster at 64×8000×2048, other summation order — profiles/README.md).
+    engine "lib" is the pointwise conv's route over its [N·H·W, C] view,
+    compose2 + the library GEMM; FLREID_NO_FUSED_1X1=1 switches it off.
 
-def adaptive_linear_1x1(x2d: torch.Tensor, gw2d: torch.Tensor,
-                        atten: Optional[torch.Tensor],
-                        aw2d: Optional[torch.Tensor],
-                        bias: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    """Dispatcher for the fused 1×1 route; None when out of regime."""
-    if (not x2d.is_cuda or not extension_available()
-            or os.environ.get("FLREID_NO_FUSED_1X1", "0") == "1"):
+    Every route needs a bf16 x2d or autocast — except the composing K2
+    route, which runs in bf16 and returns bf16 whether or not autocast is on
+    (its kernel reads fp32 weights and rounds them itself)."""
+    if not x2d.is_cuda or x2d.dim() != 2 or not extension_available():
         return None
-    if gw2d.requires_grad or (atten is not None and atten.requires_grad):
+    if engine == "lib" and os.environ.get("FLREID_NO_FUSED_1X1", "0") == "1":
         return None
-    if x2d.dtype != torch.bfloat16 and not torch.is_autocast_enabled():
+    k = weight.shape[-1]
+    ready = weight.dtype == torch.bfloat16 and atten is None and aw is None
+    if ready:
+        if not weight.is_contiguous():
+            return None
+        if k % 32 or os.environ.get("FLREID_CLASSIFIER_GEMM", "k2") == "lib":
+            engine = "lib"
+    elif (weight.requires_grad or (atten is not None and atten.requires_grad)
+          or weight.dtype != torch.float32
+          or (aw is not None and aw.dtype != torch.float32)):
         return None
-    if gw2d.dtype != torch.float32 or (aw2d is not None
-                                       and aw2d.dtype != torch.float32):
+    elif engine == "k2" and (atten is None or aw is None or k % 32
+                             or atten.numel() != k):
         return None
-    return _AdaptiveLinear1x1Fn.apply(x2d, gw2d, atten, aw2d, bias)
+    if (x2d.dtype != torch.bfloat16 and not torch.is_autocast_enabled()
+            and (ready or engine != "k2")):
+        return None
+    return _AdaptiveLinearFn.apply(x2d, weight, atten, aw, bias, engine)
 
 
 def conv_theta_tile(ext, w: torch.Tensor, atten: Optional[torch.Tensor],
@@ -1328,7 +1292,7 @@ class _Conv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, atten, aw):
-        ext = _ext_or_raise("conv3x3_img_fwd")
+        ext = require_extension("conv3x3_img_fwd")
         x_bf = _cl(x.detach().to(torch.bfloat16))
         n, c, h, w = x_bf.shape
         k = weight.shape[0]
@@ -1355,7 +1319,7 @@ class _Conv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        ext = _ext_or_raise("conv3x3_img_fwd")
+        ext = require_extension("conv3x3_img_fwd")
         x_bf, weight, atten, aw, theta = ctx.saved_tensors
         n, c, h, w = x_bf.shape
         k = weight.shape[0]
@@ -1467,7 +1431,7 @@ def conv3x3_fwd_nhwc(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     k = weight.shape[0]
     if c % 32 != 0 or k % 16 != 0:
         return torch.nn.functional.conv2d(x, weight.to(x.dtype), padding=1)
-    ext = _ext_or_raise("conv3x3_fwd")
+    ext = require_extension("conv3x3_fwd")
     assert x.is_contiguous(memory_format=torch.channels_last)
     wcl = weight.detach()
     if not wcl.is_contiguous(memory_format=torch.channels_last):
@@ -1606,7 +1570,7 @@ def head_step(rows, partials: torch.Tensor, lr: float, beta1: float,
         _head_step_cpu(rows, partials, lr, beta1, beta2, weight_decay, eps,
                        lam)
         return
-    ext = _ext_or_raise("head_step")
+    ext = require_extension("head_step")
     if ext is None:
         raise RuntimeError("head_step has no eager GPU path")
     table, off = [], 0

@@ -132,20 +132,8 @@ extern "C" void flreid_ce_smooth(const void* score, const int64_t* target,
 }
 
 // --------------------------------------------------------------------------
-// FedSTIL composition: theta = atten[i % L] * gw + aw (atten over last dim)
+// FedSTIL composition: theta = atten * gw + aw (atten over the last dim)
 // --------------------------------------------------------------------------
-
-template <typename T>
-__global__ void compose_kernel(const T* __restrict__ gw,
-                               const float* __restrict__ atten,
-                               const T* __restrict__ aw, T* __restrict__ out,
-                               int64_t numel, int64_t L) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= numel) return;
-  const float a = atten[i % L];
-  store_from_float(out, i,
-                   fmaf(a, load_as_float(gw, i), load_as_float(aw, i)));
-}
 
 // compose2: layout-aware + mixed-dtype composition.  atten broadcasts over
 // the LOGICAL last weight dim; for channels-last conv weights the physical
@@ -251,24 +239,6 @@ extern "C" void flreid_compose2(const void* gw, const float* atten,
                        (__hip_bfloat16*)out, numel, L, inner);
   } else {
     throw std::runtime_error("compose2: unsupported dtype combination");
-  }
-  HIP_CHECK(hipGetLastError());
-}
-
-extern "C" void flreid_compose(const void* gw, const float* atten,
-                               const void* aw, void* out, int64_t numel,
-                               int64_t L, int dtype, hipStream_t stream) {
-  constexpr int BLOCK = 256;
-  dim3 grid((unsigned)((numel + BLOCK - 1) / BLOCK)), block(BLOCK);
-  if (dtype == kF32) {
-    hipLaunchKernelGGL((compose_kernel<float>), grid, block, 0, stream,
-                       (const float*)gw, atten, (const float*)aw, (float*)out,
-                       numel, L);
-  } else {
-    hipLaunchKernelGGL((compose_kernel<__hip_bfloat16>), grid, block, 0,
-                       stream, (const __hip_bfloat16*)gw, atten,
-                       (const __hip_bfloat16*)aw, (__hip_bfloat16*)out, numel,
-                       L);
   }
   HIP_CHECK(hipGetLastError());
 }

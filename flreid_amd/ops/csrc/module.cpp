@@ -43,7 +43,6 @@ PYBIND11_MODULE(_flreid_hip, m) {
 
   FLREID_DEF(l2norm_rows);
   FLREID_DEF(ce_smooth);
-  FLREID_DEF(compose);
   FLREID_DEF(compose2);
   FLREID_DEF(bn_eval);
   FLREID_DEF(pairwise);

@@ -27,9 +27,6 @@ void flreid_l2norm_rows(const void* x, void* y, int64_t rows, int64_t cols,
 void flreid_ce_smooth(const void* score, const int64_t* target,
                       float* row_loss, void* grad, int64_t B, int64_t C,
                       int dtype, float eps, hipStream_t stream);
-void flreid_compose(const void* gw, const float* atten, const void* aw,
-                    void* out, int64_t numel, int64_t L, int dtype,
-                    hipStream_t stream);
 // atten / aw may be null (no scaling / no addend)
 void flreid_compose2(const void* gw, const float* atten, const void* aw,
                      void* out, int64_t numel, int64_t L, int64_t inner,

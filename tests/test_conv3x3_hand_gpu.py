@@ -168,7 +168,7 @@ TILE_CASES = [(mode, ck) for mode in (0, 1, 2)
                          ids=["mode%d-C%dK%d" % (m, c, k)
                               for m, (c, k) in TILE_CASES])
 def test_theta_tile_layouts(mode, ck, compose, dtype):
-    ext = ops._ext_or_raise("conv3x3_tile")
+    ext = ops.require_extension("conv3x3_tile")
     c, k = ck
     for kind in ("grid", "full"):
         inp = (co.grid_inputs if kind == "grid" else co.full_inputs)(

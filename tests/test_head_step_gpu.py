@@ -86,7 +86,7 @@ def _check(name, fused, unfused, want64, report):
 def test_kernel_matches_unfused_chain(grad_dtype, lam, wd):
     from flreid_amd import ops
     from flreid_amd.ops import reference as ref
-    ext = ops._ext_or_raise("head_step")
+    ext = ops.require_extension("head_step")
     data = _tensors(grad_dtype)
     lam32 = torch.tensor(lam, dtype=torch.float32, device=DEV)
 
@@ -188,7 +188,7 @@ def test_validation_mismatched_strides_raises():
 
 def test_validation_null_pointer_raises():
     from flreid_amd import ops
-    ext = ops._ext_or_raise("head_step")
+    ext = ops.require_extension("head_step")
     row, d = _one_row()
     partials = torch.zeros(1, dtype=torch.float64, device=DEV)
     row_missing = dict(row, m=None)
@@ -495,7 +495,7 @@ def test_live_theta_scope(monkeypatch):
     monkeypatch.setenv("FLREID_FUSED_HEAD_STEP", "1")
     monkeypatch.setenv("FLREID_LIVE_THETA", "1")
     from flreid_amd import ops
-    ext = ops._ext_or_raise("compose2")
+    ext = ops.require_extension("compose2")
     model, op = _build()
     (x, t), = _batches(1, (4, 4))
     with _epoch(model, op):

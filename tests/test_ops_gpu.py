@@ -528,7 +528,7 @@ def test_l1_drift_eligibility_and_anchor_lifetime():
 
 def test_adaptive_conv1x1_fused_route(monkeypatch):
     """Default-on fused pointwise route (compose2-to-bf16 + bf16 hipBLASLt,
-    _AdaptiveLinear1x1Fn) vs the eager compose+linear fallback."""
+    _AdaptiveLinearFn's lib engine) vs the eager compose+linear fallback."""
     import copy
     from flreid_amd.models.adaptive import AdaptiveConv2d
     torch.manual_seed(4)
@@ -679,7 +679,7 @@ def test_conv3x3_auto_dgrad_is_forward_conv_on_flipped_theta(monkeypatch):
     tile); conv shapes with C != K both ways and the benchmark's layer4
     shape.  (Whether repeated calls agree bit for bit depends on the solver
     the library picks, so that is not asserted here.)"""
-    ext = ops._ext_or_raise("conv3x3_tile")
+    ext = ops.require_extension("conv3x3_tile")
     torch.manual_seed(4)
     th = _cl4(torch.randn(40, 24, 3, 3, device="cuda").bfloat16())
     expect = th.float().flip(2, 3).transpose(0, 1)
