@@ -48,20 +48,24 @@ __global__ __launch_bounds__(256) void patch_merge_ln_fwd_kernel(
   const int64_t rem = row - b * ncols;
   const int ho = (int)(rem / out_w), wo = (int)(rem % out_w);
 
-  float sum = 0.f, sq = 0.f;
+  float sum = 0.f;
   for (int c4 = lane; c4 < C4; c4 += 64) {
-    const float v = load_as_float(
-        X, pm_src_index(b, 0, c4, C, H, W, out_w, ho, wo));
-    sum += v;
-    sq += v * v;
+    sum += load_as_float(X, pm_src_index(b, 0, c4, C, H, W, out_w, ho, wo));
   }
   sum = wave_reduce_sum(sum);
+  const float mean = __shfl(sum, 0, 64) / C4;
+  // variance of the CENTRED values: E[x²] − mean² loses the spread of a row
+  // whose mean is large against it (12× the centred form's error bound at
+  // mean/σ = 64).  The row, ≤ 12 KB, is cache-resident for this second read
+  float sq = 0.f;
+  for (int c4 = lane; c4 < C4; c4 += 64) {
+    const float v = load_as_float(
+        X, pm_src_index(b, 0, c4, C, H, W, out_w, ho, wo)) - mean;
+    sq += v * v;
+  }
   sq = wave_reduce_sum(sq);
-  sum = __shfl(sum, 0, 64);
-  sq = __shfl(sq, 0, 64);
-  const float mean = sum / C4;
-  const float var = sq / C4 - mean * mean;
-  const float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+  const float var = __shfl(sq, 0, 64) / C4;
+  const float rstd = rsqrtf(var + eps);
   if (lane == 0) {
     MEAN[row] = mean;
     RSTD[row] = rstd;

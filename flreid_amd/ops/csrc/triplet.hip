@@ -85,7 +85,11 @@ __global__ __launch_bounds__(256) void triplet_fwd_kernel(
       }
     }
     row_loss[i] = fmaxf(0.0f, margin + ap - an);
-    p_idx[i] = pi;
+    // an anchor whose positives are all copies of itself (a class of one):
+    // the maximum is 0 and may sit on a negative's masked column, through
+    // which the reference sends no gradient.  Record the anchor itself —
+    // f_i − f_p is then 0 in the backward; ap, and so the loss, is unchanged
+    p_idx[i] = (labels[pi] == li) ? pi : i;
     n_idx[i] = nidx;
   }
 }
