@@ -179,6 +179,44 @@ def bench_penalty(results, n):
             / (results[f"penalty_fused_s{s}"] / 1e3) / 1e9, 0)
 
 
+def bench_window_mfma(results, n):
+    """K3 at the 384² / window-12 geometry: fwd+bwd of the MFMA route
+    (window_attn_mfma.hip) against ref.window_attention on the same tensors
+    — 1024 windows × 4 heads × 144 tokens × 32, bf16, shift mask of 64
+    windows.  Seven rounds, fused and eager alternating; the median round
+    and the min / max of the rounds are reported.  TFps counts the 14 N²·D
+    matrix FLOPs per (window, head) the backward-with-recompute algorithm
+    needs (S, PV; S again, dP, dV, dQ, dK), over the fused median."""
+    bw, h, nt, d, nw = 1024, 4, 144, 32, 64
+    q, k, v, do = (torch.randn(bw, h, nt, d, device="cuda").bfloat16()
+                   for _ in range(4))
+    q, k, v = (t.requires_grad_(True) for t in (q, k, v))
+    bias = torch.randn(h, nt, nt, device="cuda", requires_grad=True)
+    mask = torch.where(torch.rand(nw, nt, nt, device="cuda") < 0.3,
+                       -100.0, 0.0)
+    mask[:, torch.arange(nt), torch.arange(nt)] = 0.0
+    assert ops.window_attention_route(nt, d, q.dtype, 0.0) == "mfma"
+
+    def run(fn):
+        fn(q, k, v, bias, mask, d ** -0.5).backward(do)
+        q.grad = k.grad = v.grad = bias.grad = None
+
+    rounds = {"fused": [], "eager": []}
+    for _ in range(1 if n == 1 else 7):
+        rounds["fused"].append(bench(lambda: run(ops.window_attention),
+                                     min(n, 10), warmup=2))
+        rounds["eager"].append(bench(lambda: run(ref.window_attention),
+                                     min(n, 10), warmup=2))
+    for tag, ts in rounds.items():
+        ts.sort()
+        results[f"window_attn_mfma_fwdbwd_{tag}"] = ts[len(ts) // 2]
+        results[f"window_attn_mfma_fwdbwd_{tag}_min"] = ts[0]
+        results[f"window_attn_mfma_fwdbwd_{tag}_max"] = ts[-1]
+    flops = 14 * bw * h * nt * nt * d
+    results["window_attn_mfma_fwdbwd_fused_TFps"] = round(
+        flops / (results["window_attn_mfma_fwdbwd_fused"] / 1e3) / 1e12, 1)
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
@@ -195,11 +233,17 @@ def main():
                    help="run only the FedSTIL one-pass head update entry")
     p.add_argument("--penalty-only", action="store_true",
                    help="run only the quadratic-penalty entry")
+    p.add_argument("--window-mfma-only", action="store_true",
+                   help="run only the 144-token window attention entry")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
 
+    if args.window_mfma_only:
+        bench_window_mfma(results, n)
+        report(results)
+        return
     if args.penalty_only:
         bench_penalty(results, n)
         report(results)
@@ -251,6 +295,8 @@ def main():
             lambda: ops.window_attention(q, k, v, bias, None, 0.18), n)
         results["window_attn_eager"] = bench(
             lambda: ref.window_attention(q, k, v, bias, None, 0.18), n)
+    del q, k, v, bias
+    bench_window_mfma(results, n)
 
     # K11: rowwise L2 normalize
     x = torch.randn(16384, 2048, device="cuda")

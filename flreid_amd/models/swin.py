@@ -6,9 +6,13 @@ reference wrapper: input resized to 224², 4 stages of shifted-window blocks,
 LN + token avgpool, BNNeck head, dual train/eval outputs
 (ref:models/swin_transformer.py:604-700).
 
-MI355X notes: the per-window attention (49 tokens) runs through
-flreid_amd.ops.window_attention — eager composition on CPU, the fused
-CDNA4 MFMA kernel (K3 in SURVEY.md §2.9) on GPU.  Staged execution
+MI355X notes: the per-window attention runs through
+flreid_amd.ops.window_attention (K3 in SURVEY.md §2.9) — eager composition
+on CPU; on GPU `ops.window_attention_route` picks the kernel: windows of up
+to 64 tokens and head dim up to 64 (49 tokens at 224² / window 7) take the
+fused VALU kernel (window_attn.hip, fp32 or bf16), bf16 windows of 65..144
+tokens at head dim 32 (144 tokens at 384² / window 12) the MFMA kernel
+(window_attn_mfma.hip), everything else the eager chain.  Staged execution
 (`stage_of`/`run_stages`) mirrors models/resnet.py so FedSTIL's head-only
 training path works unchanged (stages: stem, layers.0-3, head).
 """

@@ -632,20 +632,102 @@ class _WindowAttnFn(torch.autograd.Function):
         return dq, dk, dv, dbias, None, None
 
 
+def _window_attn_mfma_fwd_raw(ext, q, k, v, bias, mask, scale):
+    bw, h, n, d = q.shape
+    qc, kc, vc = q.contiguous(), k.contiguous(), v.contiguous()
+    bias_c = bias.detach().contiguous().float()
+    if mask is not None:
+        mask_c = mask.detach().contiguous().float()
+        nw = mask_c.shape[0]
+        mask_ptr = mask_c.data_ptr()
+    else:
+        mask_c, nw, mask_ptr = None, 1, 0
+    out = torch.empty_like(qc)
+    ext.window_attn_mfma_fwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                             bias_c.data_ptr(), mask_ptr, out.data_ptr(),
+                             bw, h, n, d, nw, float(scale), _stream())
+    return out, qc, kc, vc, bias_c, mask_c
+
+
+class _WindowAttnMfmaFn(torch.autograd.Function):
+    """Swin window MHSA fwd+bwd for 65..144-token windows (bf16, D = 32;
+    window_attn_mfma.hip).  The backward recomputes P, emits dQ/dK/dV in
+    bf16 and one fp32 [N, N] dS partial per run of `window_attn_mfma_group`
+    windows of a head; dbias is the sum of those partials."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, mask, scale):
+        ext = require_extension("window_attn_mfma_fwd")
+        out, qc, kc, vc, bias_c, mask_c = _window_attn_mfma_fwd_raw(
+            ext, q.detach(), k.detach(), v.detach(), bias, mask, scale)
+        ctx.save_for_backward(qc, kc, vc, bias_c)
+        ctx.mask_c = mask_c
+        ctx.scale = float(scale)
+        ctx.bias_requires = bias.requires_grad
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ext = require_extension("window_attn_mfma_bwd")
+        qc, kc, vc, bias_c = ctx.saved_tensors
+        mask_c = ctx.mask_c
+        bw, h, n, d = qc.shape
+        nw = mask_c.shape[0] if mask_c is not None else 1
+        go = grad_out.contiguous().to(qc.dtype)
+        dq = torch.empty_like(qc)
+        dk = torch.empty_like(kc)
+        dv = torch.empty_like(vc)
+        group = ext.window_attn_mfma_group()
+        part = torch.empty((bw + group - 1) // group, h, n, n,
+                           device=qc.device, dtype=torch.float32)
+        ext.window_attn_mfma_bwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                                 bias_c.data_ptr(),
+                                 mask_c.data_ptr() if mask_c is not None else 0,
+                                 go.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                                 dv.data_ptr(), part.data_ptr(), bw, h, n, d,
+                                 nw, ctx.scale, _stream())
+        dbias = part.sum(dim=0) if ctx.bias_requires else None
+        return dq, dk, dv, dbias, None, None
+
+
+def window_attention_route(n: int, d: int, dtype, drop_p: float) -> str:
+    """Which path serves an [.., n, d] window on the GPU with the extension
+    built: "valu" (window_attn.hip), "mfma" (window_attn_mfma.hip) or
+    "eager" (reference.window_attention)."""
+    if drop_p != 0.0:
+        return "eager"
+    if n <= 64 and d <= 64:
+        return "valu"
+    if dtype == torch.bfloat16 and d == 32 and 64 < n <= 144:
+        return "mfma"
+    return "eager"
+
+
 def window_attention(q, k, v, bias, mask, scale, dropout=None):
     """Swin window MHSA (K3): fused HIP kernels on GPU — eval forward AND
     the training fwd+bwd (dropout-free, the Swin-ReID default); eager
-    composition on CPU or when attention dropout is active."""
+    composition on CPU, when attention dropout is active or outside the
+    shapes `window_attention_route` gives to a kernel."""
     drop_p = 0.0
     if dropout is not None:
         drop_p = float(getattr(dropout, "p", 0.0))
-    if (q.is_cuda and q.shape[-2] <= 64 and q.shape[-1] <= 64
-            and drop_p == 0.0 and extension_available()):
+    route = "eager"
+    if q.is_cuda and extension_available():
+        route = window_attention_route(q.shape[-2], q.shape[-1], q.dtype,
+                                       drop_p)
+    if route == "valu":
         if not torch.is_grad_enabled():
             ext = require_extension("window_attn_fwd")
             out, *_ = _window_attn_fwd_raw(ext, q, k, v, bias, mask, scale)
             return out
         return _WindowAttnFn.apply(q, k, v, bias, mask, scale)
+    if route == "mfma":
+        if not torch.is_grad_enabled():
+            ext = require_extension("window_attn_mfma_fwd")
+            out, *_ = _window_attn_mfma_fwd_raw(ext, q, k, v, bias, mask,
+                                                scale)
+            return out
+        return _WindowAttnMfmaFn.apply(q, k, v, bias, mask, scale)
     return ref.window_attention(q, k, v, bias, mask, scale, dropout)
 
 

@@ -11,11 +11,17 @@ import os
 import subprocess
 import sys
 import sysconfig
+import tempfile
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_flreid_hip.so")
 
-SOURCES = ["module.cpp", "elementwise.hip", "distance.hip", "window_attn.hip", "triplet.hip", "adaptive_gemm.hip", "conv3x3.hip", "conv3x3_img.hip", "conv3x3_img_ldsw.hip", "bn_train.hip", "drift.hip", "kd.hip", "patch_merge.hip", "decomposed.hip", "head_step.hip", "penalty.hip"]
+SOURCES = ["module.cpp", "elementwise.hip", "distance.hip", "window_attn.hip", "window_attn_mfma.hip", "triplet.hip", "adaptive_gemm.hip", "conv3x3.hip", "conv3x3_img.hip", "conv3x3_img_ldsw.hip", "bn_train.hip", "drift.hip", "kd.hip", "patch_merge.hip", "decomposed.hip", "head_step.hip", "penalty.hip"]
+
+# Compiled on their own with the packed-fp32 instructions (v_pk_mul_f32 and
+# kin) switched off: their fp32 work sits on MFMA accumulator quads, which the
+# compiler would otherwise pair up into packed operations.
+SCALAR_FP32_SOURCES = ["window_attn_mfma.hip"]
 
 
 def _pybind11_includes():
@@ -56,16 +62,28 @@ def build(force: bool = False, arch: str = "gfx950", verbose: bool = True,
         # host-side ASan only: device code stays uninstrumented (xnack-free)
         extra = ["-fsanitize=address", "-shared-libsan",
                  "-Xarch_device", "-fno-sanitize=all"]
-    cmd = [
-        hipcc, f"--offload-arch={arch}", *opt, *extra, "-std=c++17", "-fPIC",
-        "-shared", "-fvisibility=hidden",
-        *[f"-I{p}" for p in includes],
-        *[os.path.join(CSRC, s) for s in SOURCES],
-        "-o", OUT,
-    ]
-    if verbose:
-        print("[flreid build]", " ".join(cmd))
-    subprocess.run(cmd, check=True)
+    common = [hipcc, f"--offload-arch={arch}", *opt, *extra, "-std=c++17",
+              "-fPIC", "-fvisibility=hidden", *[f"-I{p}" for p in includes]]
+    with tempfile.TemporaryDirectory() as tmp:
+        objects = []
+        for s in SCALAR_FP32_SOURCES:
+            obj = os.path.join(tmp, os.path.splitext(s)[0] + ".o")
+            # the host pass does not know the feature and says so; harmless
+            cmd = [*common, "-Xclang", "-target-feature", "-Xclang",
+                   "-packed-fp32-ops", "-c", os.path.join(CSRC, s), "-o", obj]
+            if verbose:
+                print("[flreid build]", " ".join(cmd))
+            subprocess.run(cmd, check=True)
+            objects.append(obj)
+        cmd = [*common, "-shared",
+               *[os.path.join(CSRC, s) for s in SOURCES
+                 if s not in SCALAR_FP32_SOURCES],
+               # hipcc reads every bare input as HIP source: hand the
+               # objects to the linker
+               *[f"-Wl,{o}" for o in objects], "-o", OUT]
+        if verbose:
+            print("[flreid build]", " ".join(cmd))
+        subprocess.run(cmd, check=True)
     return OUT
 
 

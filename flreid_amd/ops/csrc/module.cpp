@@ -49,6 +49,9 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(rowsq);
   FLREID_DEF(window_attn_fwd);
   FLREID_DEF(window_attn_bwd);
+  FLREID_DEF(window_attn_mfma_group);
+  FLREID_DEF(window_attn_mfma_fwd);
+  FLREID_DEF(window_attn_mfma_bwd);
   FLREID_DEF(triplet_fwd);
   FLREID_DEF(triplet_bwd);
   FLREID_DEF(adaptive_linear_fwd);

@@ -57,6 +57,22 @@ void flreid_window_attn_bwd(const void* q, const void* k, const void* v,
                             float* ds, int64_t BW, int H, int N, int D, int nW,
                             float scale, int dtype, hipStream_t stream);
 
+// ---- window_attn_mfma.hip -------------------------------------------------
+// bf16 only, D == 32, 64 < N <= 144; every pointer 16-byte aligned.
+// host helper: windows per backward workgroup; dbias_part is
+// [ceil(BW / group)][H][N][N] fp32, summed over its first axis by the caller
+int flreid_window_attn_mfma_group();
+void flreid_window_attn_mfma_fwd(const void* q, const void* k, const void* v,
+                                 const float* bias, const float* mask,
+                                 void* out, int64_t BW, int H, int N, int D,
+                                 int nW, float scale, hipStream_t stream);
+void flreid_window_attn_mfma_bwd(const void* q, const void* k, const void* v,
+                                 const float* bias, const float* mask,
+                                 const void* dout, void* dq, void* dk,
+                                 void* dv, float* dbias_part, int64_t BW,
+                                 int H, int N, int D, int nW, float scale,
+                                 hipStream_t stream);
+
 // ---- triplet.hip ----------------------------------------------------------
 void flreid_triplet_fwd(const float* F, const float* norms,
                         const int64_t* labels, float* row_loss, int* p_idx,
