@@ -217,6 +217,52 @@ def bench_window_mfma(results, n):
         flops / (results["window_attn_mfma_fwdbwd_fused"] / 1e3) / 1e12, 1)
 
 
+def bench_window_qkv(results, n):
+    """K3 at the 224² / window-7 geometry of swin-tiny stage 0, from the
+    packed projection output: `ops.window_attention_qkv` on a [4096, 49, 288]
+    bf16 qkv (3 heads, shift mask of 64 windows, bias with grad), "packed"
+    route (window_attn_qkv.hip) against the "unpacked" route (split, three
+    .contiguous() copies, the VALU kernel, transpose back, restack of the
+    three gradients) on the same tensors.  fwd+bwd, and the forward alone
+    under no_grad.  Seven rounds, alternating; median, min and max."""
+    bw, h, nt, d, nw = 4096, 3, 49, 32, 64
+    qkv = torch.randn(bw, nt, 3 * h * d, device="cuda").bfloat16()
+    qkv.requires_grad_(True)
+    do = torch.randn(bw, nt, h * d, device="cuda").bfloat16()
+    bias = torch.randn(h, nt, nt, device="cuda", requires_grad=True)
+    mask = torch.where(torch.rand(nw, nt, nt, device="cuda") < 0.3,
+                       -100.0, 0.0)
+    mask[:, torch.arange(nt), torch.arange(nt)] = 0.0
+    assert ops.window_attention_qkv_route(nt, d, qkv.dtype, 0.0) == "packed"
+    packed_route = ops.window_attention_qkv_route
+
+    def fwdbwd():
+        ops.window_attention_qkv(qkv, h, bias, mask, d ** -0.5).backward(do)
+        qkv.grad = bias.grad = None
+
+    def fwd():
+        with torch.no_grad():
+            ops.window_attention_qkv(qkv, h, bias, mask, d ** -0.5)
+
+    rounds = {}
+    try:
+        for _ in range(1 if n == 1 else 7):
+            for tag, route in (("packed", packed_route),
+                               ("unpacked", lambda *a: "unpacked")):
+                ops.window_attention_qkv_route = route
+                for what, fn in (("fwdbwd", fwdbwd), ("fwd", fwd)):
+                    rounds.setdefault(f"window_attn_qkv_{what}_{tag}",
+                                      []).append(
+                        bench(fn, min(n, 10), warmup=2))
+    finally:
+        ops.window_attention_qkv_route = packed_route
+    for key, ts in rounds.items():
+        ts.sort()
+        results[key] = ts[len(ts) // 2]
+        results[key + "_min"] = ts[0]
+        results[key + "_max"] = ts[-1]
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
@@ -235,6 +281,9 @@ def main():
                    help="run only the quadratic-penalty entry")
     p.add_argument("--window-mfma-only", action="store_true",
                    help="run only the 144-token window attention entry")
+    p.add_argument("--window-qkv-only", action="store_true",
+                   help="run only the packed-qkv 49-token window attention "
+                        "entry")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
@@ -242,6 +291,10 @@ def main():
 
     if args.window_mfma_only:
         bench_window_mfma(results, n)
+        report(results)
+        return
+    if args.window_qkv_only:
+        bench_window_qkv(results, n)
         report(results)
         return
     if args.penalty_only:
@@ -297,6 +350,7 @@ def main():
             lambda: ref.window_attention(q, k, v, bias, None, 0.18), n)
     del q, k, v, bias
     bench_window_mfma(results, n)
+    bench_window_qkv(results, n)
 
     # K11: rowwise L2 normalize
     x = torch.randn(16384, 2048, device="cuda")

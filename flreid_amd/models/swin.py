@@ -7,14 +7,20 @@ LN + token avgpool, BNNeck head, dual train/eval outputs
 (ref:models/swin_transformer.py:604-700).
 
 MI355X notes: the per-window attention runs through
-flreid_amd.ops.window_attention (K3 in SURVEY.md §2.9) — eager composition
-on CPU; on GPU `ops.window_attention_route` picks the kernel: windows of up
-to 64 tokens and head dim up to 64 (49 tokens at 224² / window 7) take the
-fused VALU kernel (window_attn.hip, fp32 or bf16), bf16 windows of 65..144
-tokens at head dim 32 (144 tokens at 384² / window 12) the MFMA kernel
-(window_attn_mfma.hip), everything else the eager chain.  Staged execution
-(`stage_of`/`run_stages`) mirrors models/resnet.py so FedSTIL's head-only
-training path works unchanged (stages: stem, layers.0-3, head).
+flreid_amd.ops.window_attention_qkv (K3 in SURVEY.md §2.9) on the qkv
+projection output as it lies.  On GPU `ops.window_attention_qkv_route` gives
+bf16 windows of up to 64 tokens at head dim 32 without attention dropout (49
+tokens at 224² / window 7 under autocast) to the packed MFMA kernel
+(window_attn_qkv.hip): no q / k / v copies, the result ready for `proj`, one
+dqkv in the backward.  Everything else is split into q, k, v and goes through
+`ops.window_attention` — eager composition on CPU; on GPU
+`ops.window_attention_route` picks the kernel: windows of up to 64 tokens and
+head dim up to 64 take the fused VALU kernel (window_attn.hip, fp32 or bf16),
+bf16 windows of 65..144 tokens at head dim 32 (144 tokens at 384² / window
+12) the MFMA kernel (window_attn_mfma.hip), the rest the eager chain.
+Staged execution (`stage_of`/`run_stages`) mirrors models/resnet.py so
+FedSTIL's head-only training path works unchanged (stages: stem, layers.0-3,
+head).
 """
 
 from __future__ import annotations
@@ -88,14 +94,12 @@ class WindowAttention(nn.Module):
 
     def forward(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None):
         bn, n, c = x.shape
-        qkv = self.qkv(x).view(bn, n, 3, self.num_heads, c // self.num_heads)
-        q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)       # [bn, h, n, d]
         bias = self.relative_position_bias_table[
             self.relative_position_index.view(-1)].view(n, n, -1)
         bias = bias.permute(2, 0, 1).contiguous()            # [h, n, n]
-        out = ops.window_attention(q, k, v, bias * 1.0, mask, self.scale,
-                                   self.attn_drop if self.training else None)
-        out = out.transpose(1, 2).reshape(bn, n, c)
+        out = ops.window_attention_qkv(
+            self.qkv(x), self.num_heads, bias * 1.0, mask, self.scale,
+            self.attn_drop if self.training else None)       # [bn, n, c]
         return self.proj_drop(self.proj(out))
 
 

@@ -731,6 +731,101 @@ def window_attention(q, k, v, bias, mask, scale, dropout=None):
     return ref.window_attention(q, k, v, bias, mask, scale, dropout)
 
 
+def _window_attn_qkv_fwd_raw(ext, qkv, num_heads, bias, mask, scale):
+    bw, n, c3 = qkv.shape
+    bias_c = bias.detach().contiguous().float()
+    if mask is not None:
+        mask_c = mask.detach().contiguous().float()
+        nw = mask_c.shape[0]
+        mask_ptr = mask_c.data_ptr()
+    else:
+        mask_c, nw, mask_ptr = None, 1, 0
+    out = torch.empty(bw, n, c3 // 3, device=qkv.device, dtype=qkv.dtype)
+    ext.window_attn_qkv_fwd(qkv.data_ptr(), bias_c.data_ptr(), mask_ptr,
+                            out.data_ptr(), bw, num_heads, n, nw,
+                            float(scale), _stream())
+    return out, bias_c, mask_c
+
+
+class _WindowAttnQkvFn(torch.autograd.Function):
+    """Swin window MHSA fwd+bwd on the packed projection output
+    [BW, N, 3·H·32] (bf16, up to 64 tokens; window_attn_qkv.hip).  Saves
+    qkv itself; the backward recomputes P, writes one dqkv in full and one
+    fp32 [N, N] dS partial per run of `window_attn_qkv_group` windows of a
+    head; dbias is the sum of those partials."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads, bias, mask, scale):
+        ext = require_extension("window_attn_qkv_fwd")
+        qkv_d = qkv.detach()
+        out, bias_c, mask_c = _window_attn_qkv_fwd_raw(
+            ext, qkv_d, num_heads, bias, mask, scale)
+        ctx.save_for_backward(qkv_d, bias_c)
+        ctx.mask_c = mask_c
+        ctx.num_heads = num_heads
+        ctx.scale = float(scale)
+        ctx.bias_requires = bias.requires_grad
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ext = require_extension("window_attn_qkv_bwd")
+        qkv, bias_c = ctx.saved_tensors
+        mask_c = ctx.mask_c
+        bw, n, _ = qkv.shape
+        h = ctx.num_heads
+        nw = mask_c.shape[0] if mask_c is not None else 1
+        go = grad_out.contiguous().to(qkv.dtype)
+        dqkv = torch.empty_like(qkv)
+        group = ext.window_attn_qkv_group()
+        part = torch.empty((bw + group - 1) // group, h, n, n,
+                           device=qkv.device, dtype=torch.float32)
+        ext.window_attn_qkv_bwd(qkv.data_ptr(), bias_c.data_ptr(),
+                                mask_c.data_ptr() if mask_c is not None else 0,
+                                go.data_ptr(), dqkv.data_ptr(),
+                                part.data_ptr(), bw, h, n, nw, ctx.scale,
+                                _stream())
+        dbias = part.sum(dim=0) if ctx.bias_requires else None
+        return dqkv, None, dbias, None, None
+
+
+def window_attention_qkv_route(n: int, d: int, dtype, drop_p: float) -> str:
+    """Which path serves a packed [BW, n, 3·H·d] projection output on the
+    GPU with the extension built (and the tensor contiguous): "packed"
+    (window_attn_qkv.hip) or "unpacked" (split into q, k, v and
+    `window_attention`)."""
+    if dtype == torch.bfloat16 and d == 32 and 1 <= n <= 64 and drop_p == 0.0:
+        return "packed"
+    return "unpacked"
+
+
+def window_attention_qkv(qkv, num_heads, bias, mask, scale, dropout=None):
+    """Swin window MHSA from the qkv projection output [BW, N, 3·C], last
+    axis ordered (q|k|v, head, d), to [BW, N, C] ready for `proj`.  The
+    "packed" route runs the attention on that tensor as it lies; every other
+    case splits it and goes through `window_attention`."""
+    bw, n, c3 = qkv.shape
+    c = c3 // 3
+    drop_p = 0.0
+    if dropout is not None:
+        drop_p = float(getattr(dropout, "p", 0.0))
+    route = "unpacked"
+    if qkv.is_cuda and qkv.is_contiguous() and extension_available():
+        route = window_attention_qkv_route(n, c // num_heads, qkv.dtype,
+                                           drop_p)
+    if route == "packed":
+        if not torch.is_grad_enabled():
+            ext = require_extension("window_attn_qkv_fwd")
+            out, *_ = _window_attn_qkv_fwd_raw(ext, qkv, num_heads, bias,
+                                               mask, scale)
+            return out
+        return _WindowAttnQkvFn.apply(qkv, num_heads, bias, mask, scale)
+    q, k, v = qkv.view(bw, n, 3, num_heads, c // num_heads).permute(
+        2, 0, 3, 1, 4).unbind(0)                             # [bw, h, n, d]
+    out = window_attention(q, k, v, bias, mask, scale, dropout)
+    return out.transpose(1, 2).reshape(bw, n, c)
+
+
 class _PatchMergeLNFn(torch.autograd.Function):
     """Fused Swin PatchMerging gather + LayerNorm (K4, patch_merge.hip):
     the 2×2 strided concat tensor never materialises; forward emits the

@@ -52,6 +52,9 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(window_attn_mfma_group);
   FLREID_DEF(window_attn_mfma_fwd);
   FLREID_DEF(window_attn_mfma_bwd);
+  FLREID_DEF(window_attn_qkv_group);
+  FLREID_DEF(window_attn_qkv_fwd);
+  FLREID_DEF(window_attn_qkv_bwd);
   FLREID_DEF(triplet_fwd);
   FLREID_DEF(triplet_bwd);
   FLREID_DEF(adaptive_linear_fwd);

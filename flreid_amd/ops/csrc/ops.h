@@ -73,6 +73,23 @@ void flreid_window_attn_mfma_bwd(const void* q, const void* k, const void* v,
                                  int H, int N, int D, int nW, float scale,
                                  hipStream_t stream);
 
+// ---- window_attn_qkv.hip --------------------------------------------------
+// bf16 only, D == 32, 1 <= N <= 64; every pointer 16-byte aligned.  qkv and
+// dqkv are [BW][N][3·H·32] with the last axis ordered (q|k|v, head, d); out
+// and dout are [BW][N][H·32].
+// host helper: windows per backward workgroup; dbias_part is
+// [ceil(BW / group)][H][N][N] fp32, summed over its first axis by the caller
+int flreid_window_attn_qkv_group();
+void flreid_window_attn_qkv_fwd(const void* qkv, const float* bias,
+                                const float* mask, void* out, int64_t BW,
+                                int H, int N, int nW, float scale,
+                                hipStream_t stream);
+void flreid_window_attn_qkv_bwd(const void* qkv, const float* bias,
+                                const float* mask, const void* dout,
+                                void* dqkv, float* dbias_part, int64_t BW,
+                                int H, int N, int nW, float scale,
+                                hipStream_t stream);
+
 // ---- triplet.hip ----------------------------------------------------------
 void flreid_triplet_fwd(const float* F, const float* norms,
                         const int64_t* labels, float* row_loss, int* p_idx,
