@@ -263,6 +263,56 @@ def bench_window_qkv(results, n):
         results[key + "_max"] = ts[-1]
 
 
+def bench_window_map(results, n):
+    """One attention sub-block of swin-tiny stage 0 between the qkv and proj
+    linears: `ops.shifted_window_attention_qkv` on a [64, 56, 56, 288] bf16
+    qkv map (3 heads, window 7, shift 3, bias with grad), route "map"
+    (window_attn_map.hip on the map as it lies) against route "windows"
+    (roll, partition, the packed kernel with the shift mask, reverse, roll and
+    autograd's mirror images) on the same tensors.  fwd+bwd, and the forward
+    alone under no_grad.  Seven rounds, alternating; median, min and max."""
+    from flreid_amd.models.swin import SwinBlock
+    b, hi, ws, shift, h, d = 64, 56, 7, 3, 3, 32
+    nt = ws * ws
+    qkv = torch.randn(b, hi, hi, 3 * h * d, device="cuda").bfloat16()
+    qkv.requires_grad_(True)
+    do = torch.randn(b, hi, hi, h * d, device="cuda").bfloat16()
+    bias = torch.randn(h, nt, nt, device="cuda", requires_grad=True)
+    mask = SwinBlock(h * d, (hi, hi), h, ws, shift).attn_mask.cuda()
+    map_route = ops.shifted_window_attention_qkv_route
+    assert map_route(nt, d, qkv.dtype, 0.0, hi, hi, ws, shift) == "map"
+
+    def op():
+        return ops.shifted_window_attention_qkv(qkv, h, ws, shift, bias, mask,
+                                                d ** -0.5)
+
+    def fwdbwd():
+        op().backward(do)
+        qkv.grad = bias.grad = None
+
+    def fwd():
+        with torch.no_grad():
+            op()
+
+    rounds = {}
+    try:
+        for _ in range(1 if n == 1 else 7):
+            for tag, route in (("map", map_route),
+                               ("windows", lambda *a: "windows")):
+                ops.shifted_window_attention_qkv_route = route
+                for what, fn in (("fwdbwd", fwdbwd), ("fwd", fwd)):
+                    rounds.setdefault(f"window_attn_map_{what}_{tag}",
+                                      []).append(
+                        bench(fn, min(n, 10), warmup=2))
+    finally:
+        ops.shifted_window_attention_qkv_route = map_route
+    for key, ts in rounds.items():
+        ts.sort()
+        results[key] = ts[len(ts) // 2]
+        results[key + "_min"] = ts[0]
+        results[key + "_max"] = ts[-1]
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
@@ -284,11 +334,18 @@ def main():
     p.add_argument("--window-qkv-only", action="store_true",
                    help="run only the packed-qkv 49-token window attention "
                         "entry")
+    p.add_argument("--window-map-only", action="store_true",
+                   help="run only the map-addressed shifted-window attention "
+                        "entry")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
 
+    if args.window_map_only:
+        bench_window_map(results, n)
+        report(results)
+        return
     if args.window_mfma_only:
         bench_window_mfma(results, n)
         report(results)
@@ -351,6 +408,7 @@ def main():
     del q, k, v, bias
     bench_window_mfma(results, n)
     bench_window_qkv(results, n)
+    bench_window_map(results, n)
 
     # K11: rowwise L2 normalize
     x = torch.randn(16384, 2048, device="cuda")

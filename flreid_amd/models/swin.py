@@ -6,7 +6,16 @@ reference wrapper: input resized to 224², 4 stages of shifted-window blocks,
 LN + token avgpool, BNNeck head, dual train/eval outputs
 (ref:models/swin_transformer.py:604-700).
 
-MI355X notes: the per-window attention runs through
+MI355X notes: where `ops.shifted_window_attention_qkv_route` says "map" (GPU,
+extension built, bf16 — the autocast dtype counts —, head dim 32, windows of
+up to 64 tokens that tile the map, no attention dropout) a block is
+norm1 → qkv on the feature map → window_attn_map.hip → proj → + shortcut:
+the kernel reads qkv from the map and writes its result to it in image
+order, so roll, window_partition, window_reverse and the second roll are its
+addressing, and it forms the shift mask from region labels (`attn_mask` is
+passed on but not read there).  Every other configuration runs roll /
+partition / attention / reverse / roll as before:
+the per-window attention runs through
 flreid_amd.ops.window_attention_qkv (K3 in SURVEY.md §2.9) on the qkv
 projection output as it lies.  On GPU `ops.window_attention_qkv_route` gives
 bf16 windows of up to 64 tokens at head dim 32 without attention dropout (49
@@ -92,14 +101,25 @@ class WindowAttention(nn.Module):
         self.proj_drop = nn.Dropout(proj_drop)
         nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02)
 
-    def forward(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None):
-        bn, n, c = x.shape
+    def forward(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                shift: int = 0):
+        """x [b·nW, n, c]: the windows, already rolled and partitioned, or
+        x [b, h, w, c]: the feature map in image order, whose windows are
+        those of a roll by -`shift`; the result has x's form.  `mask` is the
+        block's shift mask in both (None without a shift)."""
+        n = self.window_size * self.window_size
         bias = self.relative_position_bias_table[
             self.relative_position_index.view(-1)].view(n, n, -1)
         bias = bias.permute(2, 0, 1).contiguous()            # [h, n, n]
-        out = ops.window_attention_qkv(
-            self.qkv(x), self.num_heads, bias * 1.0, mask, self.scale,
-            self.attn_drop if self.training else None)       # [bn, n, c]
+        dropout = self.attn_drop if self.training else None
+        if x.dim() == 4:
+            out = ops.shifted_window_attention_qkv(
+                self.qkv(x), self.num_heads, self.window_size, shift,
+                bias * 1.0, mask, self.scale, dropout)       # [b, h, w, c]
+        else:
+            out = ops.window_attention_qkv(
+                self.qkv(x), self.num_heads, bias * 1.0, mask, self.scale,
+                dropout)                                     # [bn, n, c]
         return self.proj_drop(self.proj(out))
 
 
@@ -146,18 +166,42 @@ class SwinBlock(nn.Module):
         diff = windows.unsqueeze(1) - windows.unsqueeze(2)
         return diff.masked_fill(diff != 0, -100.0).masked_fill(diff == 0, 0.0)
 
+    def _on_the_map(self, x: torch.Tensor) -> bool:
+        """Whether the attention runs on the feature map as it lies
+        (`ops.shifted_window_attention_qkv`, route "map"), for the dtype the
+        qkv projection will produce."""
+        if not (x.is_cuda and ops.extension_available()):
+            return False
+        h, w = self.input_resolution
+        dtype = x.dtype
+        if torch.is_autocast_enabled("cuda"):
+            dtype = torch.get_autocast_dtype("cuda")
+        drop_p = self.attn.attn_drop.p if self.training else 0.0
+        return (h * w * 3 * self.dim * 2 < 2 ** 31
+                and ops.shifted_window_attention_qkv_route(
+                    self.window_size ** 2, self.dim // self.attn.num_heads,
+                    dtype, drop_p, h, w, self.window_size,
+                    self.shift) == "map")
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         h, w = self.input_resolution
         b, L, c = x.shape
         shortcut = x
         x = self.norm1(x).view(b, h, w, c)
-        if self.shift > 0:
-            x = torch.roll(x, shifts=(-self.shift, -self.shift), dims=(1, 2))
-        win = window_partition(x, self.window_size)            # [b·nW, N, C]
-        win = self.attn(win, self.attn_mask)
-        x = window_reverse(win, self.window_size, h, w)
-        if self.shift > 0:
-            x = torch.roll(x, shifts=(self.shift, self.shift), dims=(1, 2))
+        if self._on_the_map(x):
+            # qkv and proj are per-token: roll, partition and their inverses
+            # are addressing inside the kernel
+            x = self.attn(x, self.attn_mask, self.shift)
+        else:
+            if self.shift > 0:
+                x = torch.roll(x, shifts=(-self.shift, -self.shift),
+                               dims=(1, 2))
+            win = window_partition(x, self.window_size)        # [b·nW, N, C]
+            win = self.attn(win, self.attn_mask)
+            x = window_reverse(win, self.window_size, h, w)
+            if self.shift > 0:
+                x = torch.roll(x, shifts=(self.shift, self.shift),
+                               dims=(1, 2))
         x = shortcut + self.drop_path(x.view(b, L, c))
         return x + self.drop_path(self.mlp(self.norm2(x)))
 

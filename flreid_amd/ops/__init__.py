@@ -826,6 +826,115 @@ def window_attention_qkv(qkv, num_heads, bias, mask, scale, dropout=None):
     return out.transpose(1, 2).reshape(bw, n, c)
 
 
+def _window_attn_map_fwd_raw(ext, qkv, num_heads, ws, shift, bias, scale):
+    b, hi, wi, c3 = qkv.shape
+    bias_c = bias.detach().contiguous().float()
+    out = torch.empty(b, hi, wi, c3 // 3, device=qkv.device, dtype=qkv.dtype)
+    ext.window_attn_map_fwd(qkv.data_ptr(), bias_c.data_ptr(),
+                            out.data_ptr(), b, hi, wi, ws, shift, num_heads,
+                            float(scale), _stream())
+    return out, bias_c
+
+
+class _WindowAttnMapFn(torch.autograd.Function):
+    """Shifted-window MHSA fwd+bwd on the qkv feature map [B, Hi, Wi,
+    3·H·32] (bf16, windows of up to 64 tokens; window_attn_map.hip): roll,
+    partition, reverse and the shift mask happen inside the kernels.  Saves
+    qkv itself; the backward recomputes P, writes one dqkv in map order and
+    one fp32 [N, N] dS partial per run of `window_attn_qkv_group` windows of
+    a head; dbias is the sum of those partials."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads, ws, shift, bias, scale):
+        ext = require_extension("window_attn_map_fwd")
+        qkv_d = qkv.detach()
+        out, bias_c = _window_attn_map_fwd_raw(ext, qkv_d, num_heads, ws,
+                                               shift, bias, scale)
+        ctx.save_for_backward(qkv_d, bias_c)
+        ctx.geom = (num_heads, ws, shift)
+        ctx.scale = float(scale)
+        ctx.bias_requires = bias.requires_grad
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ext = require_extension("window_attn_map_bwd")
+        qkv, bias_c = ctx.saved_tensors
+        h, ws, shift = ctx.geom
+        b, hi, wi, _ = qkv.shape
+        n = ws * ws
+        bw = b * (hi // ws) * (wi // ws)
+        go = grad_out.contiguous().to(qkv.dtype)
+        dqkv = torch.empty_like(qkv)
+        group = ext.window_attn_qkv_group()
+        part = torch.empty((bw + group - 1) // group, h, n, n,
+                           device=qkv.device, dtype=torch.float32)
+        ext.window_attn_map_bwd(qkv.data_ptr(), bias_c.data_ptr(),
+                                go.data_ptr(), dqkv.data_ptr(),
+                                part.data_ptr(), b, hi, wi, ws, shift, h,
+                                ctx.scale, _stream())
+        dbias = part.sum(dim=0) if ctx.bias_requires else None
+        return dqkv, None, None, None, dbias, None
+
+
+def shifted_window_attention_qkv_route(n: int, d: int, dtype, drop_p: float,
+                                       hi: int, wi: int, ws: int,
+                                       shift: int) -> str:
+    """Which path serves a qkv feature map [B, hi, wi, 3·H·d] with windows of
+    n = ws² tokens on the GPU with the extension built (the tensor
+    contiguous, one image of it below 2 GiB): "map" (window_attn_map.hip on
+    the map as it lies) or "windows" (roll, partition, `window_attention_qkv`,
+    reverse, roll).  No map instance spills, so every (tile count, shifted)
+    combination inside the kernel's range is routed to it."""
+    if (dtype == torch.bfloat16 and d == 32 and ws >= 1 and n == ws * ws
+            and n <= 64 and hi % ws == 0 and wi % ws == 0
+            and 0 <= shift < ws and drop_p == 0.0):
+        return "map"
+    return "windows"
+
+
+def shifted_window_attention_qkv(qkv_map, num_heads, window_size, shift, bias,
+                                 mask, scale, dropout=None):
+    """Swin (shifted-)window MHSA from the qkv projection of the feature map,
+    [B, Hi, Wi, 3·C] with the last axis ordered (q|k|v, head, d), to
+    [B, Hi, Wi, C] in image order, ready for `proj`.  Equal to roll(-shift),
+    window partition, `window_attention_qkv` with `mask`, window reverse,
+    roll(+shift); the "windows" route is literally that.  `mask` is None when
+    shift == 0 and otherwise MUST be the standard Swin shift mask of this
+    geometry ([nW, N, N], 0 / -100 by region label, `SwinBlock._build_mask`):
+    the "map" route does not read it and forms that mask in the kernel."""
+    b, hi, wi, c3 = qkv_map.shape
+    c = c3 // 3
+    ws, n = window_size, window_size * window_size
+    drop_p = 0.0
+    if dropout is not None:
+        drop_p = float(getattr(dropout, "p", 0.0))
+    route = "windows"
+    if (qkv_map.is_cuda and qkv_map.is_contiguous() and extension_available()
+            and hi * wi * c3 * 2 < 2 ** 31):
+        route = shifted_window_attention_qkv_route(
+            n, c // num_heads, qkv_map.dtype, drop_p, hi, wi, ws, shift)
+    if route == "map":
+        if not torch.is_grad_enabled():
+            ext = require_extension("window_attn_map_fwd")
+            out, _ = _window_attn_map_fwd_raw(ext, qkv_map, num_heads, ws,
+                                              shift, bias, scale)
+            return out
+        return _WindowAttnMapFn.apply(qkv_map, num_heads, ws, shift, bias,
+                                      scale)
+    x = qkv_map
+    if shift > 0:
+        x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2))
+    win = x.view(b, hi // ws, ws, wi // ws, ws, c3).permute(
+        0, 1, 3, 2, 4, 5).reshape(-1, n, c3)                 # [b·nW, n, 3c]
+    win = window_attention_qkv(win, num_heads, bias, mask, scale, dropout)
+    x = win.view(b, hi // ws, wi // ws, ws, ws, c).permute(
+        0, 1, 3, 2, 4, 5).reshape(b, hi, wi, c)
+    if shift > 0:
+        x = torch.roll(x, shifts=(shift, shift), dims=(1, 2))
+    return x
+
+
 class _PatchMergeLNFn(torch.autograd.Function):
     """Fused Swin PatchMerging gather + LayerNorm (K4, patch_merge.hip):
     the 2×2 strided concat tensor never materialises; forward emits the

@@ -55,6 +55,8 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(window_attn_qkv_group);
   FLREID_DEF(window_attn_qkv_fwd);
   FLREID_DEF(window_attn_qkv_bwd);
+  FLREID_DEF(window_attn_map_fwd);
+  FLREID_DEF(window_attn_map_bwd);
   FLREID_DEF(triplet_fwd);
   FLREID_DEF(triplet_bwd);
   FLREID_DEF(adaptive_linear_fwd);

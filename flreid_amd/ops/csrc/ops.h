@@ -90,6 +90,26 @@ void flreid_window_attn_qkv_bwd(const void* qkv, const float* bias,
                                 int H, int N, int nW, float scale,
                                 hipStream_t stream);
 
+// ---- window_attn_map.hip --------------------------------------------------
+// The same attention on the feature map: bf16 only, D == 32, 1 <= ws <= 8,
+// Hi and Wi multiples of ws, 0 <= shift < ws, one image of qkv below 2 GiB;
+// every pointer 16-byte aligned.  qkv and dqkv are [B][Hi][Wi][3·H·32] with
+// the last axis ordered (q|k|v, head, d); out and dout are [B][Hi][Wi][H·32],
+// in image order.  The kernels do roll(-shift), the window partition, its
+// reverse and roll(+shift) by addressing, and form the standard shift mask
+// (0 / -100 by region label) of this geometry themselves when shift > 0:
+// there is no mask tensor.  bias is [H][ws²][ws²] fp32.  dbias_part is
+// [ceil(B·nW / flreid_window_attn_qkv_group())][H][ws²][ws²] fp32, nW =
+// (Hi / ws)·(Wi / ws), summed over its first axis by the caller.
+void flreid_window_attn_map_fwd(const void* qkv, const float* bias, void* out,
+                                int B, int Hi, int Wi, int ws, int shift,
+                                int H, float scale, hipStream_t stream);
+void flreid_window_attn_map_bwd(const void* qkv, const float* bias,
+                                const void* dout, void* dqkv,
+                                float* dbias_part, int B, int Hi, int Wi,
+                                int ws, int shift, int H, float scale,
+                                hipStream_t stream);
+
 // ---- triplet.hip ----------------------------------------------------------
 void flreid_triplet_fwd(const float* F, const float* norms,
                         const int64_t* labels, float* row_loss, int* p_idx,
