@@ -313,10 +313,98 @@ def bench_window_map(results, n):
         results[key + "_max"] = ts[-1]
 
 
+# one-launch tiles per flagship shape: variant id -> channels per block
+# (the instantiation table of ops/csrc/bn_onepass.hip); +256 = plain block
+# order instead of the per-XCD channel ranges
+BN_ONEPASS_TILES = {
+    (2048, 512): {0: 4, 1: 8, 2: 8},
+    (2048, 2048): {3: 8, 4: 16},
+    (64, 2048): {5: 8, 6: 16, 7: 32},
+}
+
+
+def bench_bn(results, n):
+    """Train BN fwd and bwd at the three flagship shapes (bf16): the
+    two-launch pair against every one-launch tile.  Device events around n
+    back-to-back launches, median of 5 such windows; where the figure stops
+    falling with the kernel it is the host's launch rate.  *_GBps = bytes the
+    direction must move (fwd: read x, write y; bwd: read x and dy, write dx)
+    over that time — the tensors are 0.25–8 MB and cache-resident, so this is
+    not a share of HBM bandwidth."""
+    ext = ops.require_extension("bn bench")
+    n = max(n, 1) * 4
+
+    def timed(fn):
+        for _ in range(10):
+            fn()
+        ts = []
+        for _ in range(5):
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) / n)
+        return sorted(ts)[2]
+
+    for (m, c), tiles in BN_ONEPASS_TILES.items():
+        x = torch.randn(m, c, device="cuda").bfloat16()
+        dy = torch.randn(m, c, device="cuda").bfloat16()
+        y, dx = torch.empty_like(x), torch.empty_like(x)
+        f32 = dict(device="cuda", dtype=torch.float32)
+        gamma, beta = torch.rand(c, **f32) + 0.5, torch.randn(c, **f32)
+        rm, rv = torch.zeros(c, **f32), torch.ones(c, **f32)
+        sm, si = torch.empty(c, **f32), torch.empty(c, **f32)
+        dg, db = torch.empty(c, **f32), torch.empty(c, **f32)
+        nbt = torch.zeros((), device="cuda", dtype=torch.long)
+        part = torch.empty(2, ext.bn_train_nslab(m, c), c, **f32)
+        unb = m / (m - 1)
+
+        st = torch.cuda.current_stream().cuda_stream
+        px, py, pdy, pdx = (t.data_ptr() for t in (x, y, dy, dx))
+        pg, pb, prm, prv = (t.data_ptr() for t in (gamma, beta, rm, rv))
+        psm, psi, pdg, pdb = (t.data_ptr() for t in (sm, si, dg, db))
+        pa, pbb, pn = part[0].data_ptr(), part[1].data_ptr(), nbt.data_ptr()
+
+        def fwd2():
+            ext.bn_train_fwd(px, py, pg, pb, prm, prv, psm, psi, pa, pbb, pn,
+                             m, c, 0.1, 1e-5, unb, 1, 1, st)
+
+        def bwd2():
+            ext.bn_train_bwd(px, pdy, pdx, pg, pb, psm, psi, pdg, pdb, pa,
+                             pbb, m, c, 1, 1, st)
+
+        def fwd1(v):
+            ext.bn_onepass_fwd(px, py, pg, pb, prm, prv, psm, psi, pn, m, c,
+                               0.1, 1e-5, unb, 1, v, st)
+
+        def bwd1(v):
+            ext.bn_onepass_bwd(px, pdy, pdx, pg, pb, psm, psi, pdg, pdb, m,
+                               c, 1, v, st)
+
+        tag = f"bn_m{m}_c{c}"
+        nbytes = {"fwd": 2 * m * c * 2, "bwd": 3 * m * c * 2}
+        runs = {"two_launch": (fwd2, bwd2)}
+        for v, w in tiles.items():
+            for order, vv in (("", v), ("_plain", v + 256)):
+                runs[f"one_launch_t{v}_w{w}{order}"] = (
+                    lambda vv=vv: fwd1(vv), lambda vv=vv: bwd1(vv))
+        runs["one_launch_default"] = (lambda: fwd1(-1), lambda: bwd1(-1))
+        for name, (f, b) in runs.items():
+            for d, fn in (("fwd", f), ("bwd", b)):
+                ms = timed(fn)
+                results[f"{tag}_{d}_{name}"] = ms
+                results[f"{tag}_{d}_{name}_GBps"] = round(
+                    nbytes[d] / (ms / 1e3) / 1e9, 0)
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
-        print(f"{k:28s} {v:10.3f}" + (" ms" if "_TF" not in k and "GBps" not in k else ""))
+        print(f"{k:28s} {v:10.4f}" + (" ms" if "_TF" not in k and "GBps" not in k else ""))
 
 
 def main():
@@ -337,11 +425,18 @@ def main():
     p.add_argument("--window-map-only", action="store_true",
                    help="run only the map-addressed shifted-window attention "
                         "entry")
+    p.add_argument("--bn-only", action="store_true",
+                   help="run only the train-BN entry: one-launch tiles "
+                        "against the two-launch pair")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
 
+    if args.bn_only:
+        bench_bn(results, n)
+        report(results)
+        return
     if args.window_map_only:
         bench_window_map(results, n)
         report(results)

@@ -35,7 +35,8 @@ class EvalFusedBatchNorm2d(nn.BatchNorm2d):
       - EVAL: one-pass normalize kernel (prototype capture / validation —
         the ReID hot eval paths);
       - TRAIN on small channels-last batches (the FedSTIL head epoch on
-        cached prototype features): single-kernel fwd/bwd with in-kernel
+        cached prototype features): fused fwd/bwd (one launch per direction
+        where the rows fit in registers, else two) with in-kernel
         statistics and running-stat update, replacing MIOpen's 5-kernel
         chain + fp32 autocast round-trip per layer (see ops/csrc/bn_train.hip).
     When `fuse_relu` is set (bn1/bn2 inside the residual blocks and the stem

@@ -1270,24 +1270,43 @@ def quadratic_penalty(params: Dict[str, torch.Tensor],
 class _BnTrain2dFn(torch.autograd.Function):
     """Fused training BatchNorm2d over channels-last rows (bn_train.hip).
 
-    One kernel per direction instead of MIOpen's 5-kernel chains +
-    SubTensorOp casts + the autocast fp32 round-trip; running stats update
-    inside the forward kernel (replay-safe for hipGraph capture)."""
+    Replaces MIOpen's 5-kernel chains + SubTensorOp casts + the autocast
+    fp32 round-trip.  `onepass` picks between two kernel families that give
+    the same bits: one launch per direction (bn_onepass.hip — a block owns a
+    channel group over all rows and keeps them in registers; no workspace),
+    or two launches per direction (partial sums into a workspace, then
+    finalize).  Running stats update inside the forward kernel either way
+    (replay-safe for hipGraph capture)."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps,
-                nbt, relu):
+                nbt, relu, onepass):
         ext = require_extension("bn_train")
         c = x.shape[1]
         m = x.numel() // c
         y = torch.empty_like(x)
         smean = torch.empty(c, device=x.device, dtype=torch.float32)
         sinv = torch.empty(c, device=x.device, dtype=torch.float32)
+        has_rs = running_mean is not None
+        ctx.relu = bool(relu)
+        ctx.onepass = bool(onepass)
+        if onepass:
+            ext.bn_onepass_fwd(
+                x.data_ptr(), y.data_ptr(),
+                gamma.detach().contiguous().data_ptr(),
+                beta.detach().contiguous().data_ptr(),
+                running_mean.data_ptr() if has_rs else 0,
+                running_var.data_ptr() if has_rs else 0,
+                smean.data_ptr(), sinv.data_ptr(),
+                nbt.data_ptr() if nbt is not None else 0, m, c,
+                float(momentum), float(eps), float(m) / float(m - 1),
+                int(relu), -1, _stream())
+            ctx.save_for_backward(x, gamma, beta, smean, sinv)
+            return y
         # split-row partial-sum workspace (overwritten densely every call —
         # no zeroing kernel needed)
         nslab = ext.bn_train_nslab(m, c)
         part = torch.empty(2, nslab, c, device=x.device, dtype=torch.float32)
-        has_rs = running_mean is not None
         ext.bn_train_fwd(
             x.data_ptr(), y.data_ptr(),
             gamma.detach().contiguous().data_ptr(),
@@ -1300,7 +1319,6 @@ class _BnTrain2dFn(torch.autograd.Function):
             float(momentum), float(eps), float(m) / float(m - 1),
             int(relu), _dt(x), _stream())
         ctx.save_for_backward(x, gamma, beta, smean, sinv)
-        ctx.relu = bool(relu)
         return y
 
     @staticmethod
@@ -1319,6 +1337,14 @@ class _BnTrain2dFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgamma = torch.empty(c, device=x.device, dtype=torch.float32)
         dbeta = torch.empty(c, device=x.device, dtype=torch.float32)
+        if ctx.onepass:
+            ext.bn_onepass_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(),
+                               gamma.detach().contiguous().data_ptr(),
+                               beta.detach().contiguous().data_ptr(),
+                               smean.data_ptr(), sinv.data_ptr(),
+                               dgamma.data_ptr(), dbeta.data_ptr(),
+                               m, c, int(ctx.relu), -1, _stream())
+            return dx, dgamma, dbeta, None, None, None, None, None, None, None
         nslab = ext.bn_train_nslab(m, c)
         part = torch.empty(2, nslab, c, device=x.device, dtype=torch.float32)
         ext.bn_train_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(),
@@ -1328,7 +1354,20 @@ class _BnTrain2dFn(torch.autograd.Function):
                          dgamma.data_ptr(), dbeta.data_ptr(),
                          part[0].data_ptr(), part[1].data_ptr(),
                          m, c, int(ctx.relu), _dt(x), _stream())
-        return dx, dgamma, dbeta, None, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def bn_onepass_applies(m: int, c: int, dtype: torch.dtype) -> bool:
+    """The one-launch train-BN kernels take this [M, C] problem: bf16, rows
+    per stripe small enough to stay in registers (the extension's table
+    decides), and FLREID_BN_ONEPASS not 0.  Otherwise the two-launch kernels
+    run; both give the same bits."""
+    if os.environ.get("FLREID_BN_ONEPASS", "1") == "0":
+        return False
+    if dtype != torch.bfloat16 or c % 64 != 0 or m < 2:
+        return False
+    ext = _load_extension()
+    return ext is not None and ext.bn_onepass_config(m, c) >= 0
 
 
 def bn_train_2d(x: torch.Tensor, bn,
@@ -1339,8 +1378,10 @@ def bn_train_2d(x: torch.Tensor, bn,
     count (M = N·H·W ≤ 16384 — covers the cached-prototype batches AND
     batch-64 layer-4 full-image fine-tuning at 16×8 spatial; very large M
     stays on MIOpen's multi-block reduction).  The
-    num_batches_tracked increment is fused into the forward kernel.  Returns
-    None when the fused path does not apply."""
+    num_batches_tracked increment is fused into the forward kernel.  Inside
+    that window bn_onepass_applies() picks the one-launch kernels over the
+    two-launch pair (FLREID_BN_ONEPASS=0 forces the pair).  Returns None
+    when the fused path does not apply."""
     if os.environ.get("FLREID_NO_FUSED_BN", "0") == "1":
         return None
     if (not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16)
@@ -1369,7 +1410,8 @@ def bn_train_2d(x: torch.Tensor, bn,
     else:
         rm = rv = None
     return _BnTrain2dFn.apply(x, bn.weight, bn.bias, rm, rv,
-                              bn.momentum, bn.eps, nbt, relu)
+                              bn.momentum, bn.eps, nbt, relu,
+                              bn_onepass_applies(m, c, x.dtype))
 
 
 def _cl(t: torch.Tensor) -> torch.Tensor:

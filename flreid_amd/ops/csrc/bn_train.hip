@@ -1,4 +1,8 @@
-// Fused training-mode BatchNorm2d over NHWC rows (K1-adjacent hot op).
+// Fused training-mode BatchNorm2d over NHWC rows (K1-adjacent hot op): the
+// two-launch pair.  bn_onepass.hip does the same arithmetic (bn_train.h) in
+// one launch per direction where the rows fit in registers; this pair is the
+// path for larger M and fp32, and the reference the one-launch kernels are
+// tested against bit for bit.
 //
 // MIOpen's train BN on the FedSTIL head-epoch shapes (M = N·H·W = 2048 rows,
 // C ∈ {512, 1024, 2048}) costs 5 kernels per layer per direction
@@ -30,52 +34,11 @@
 // normalisation, unbiased (·M/(M−1)) for the running-var update
 // (ref models the same torch module family: ref:models/resnet.py).
 
+#include "bn_train.h"
 #include "common.h"
 #include "ops.h"
 
 namespace flreid {
-
-template <typename T>
-__device__ __forceinline__ void bn_load4(const T* p, float v[4]);
-
-template <>
-__device__ __forceinline__ void bn_load4<float>(const float* p, float v[4]) {
-  const float4 t = *reinterpret_cast<const float4*>(p);
-  v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-
-template <>
-__device__ __forceinline__ void bn_load4<__hip_bfloat16>(
-    const __hip_bfloat16* p, float v[4]) {
-  const ushort4 t = *reinterpret_cast<const ushort4*>(p);
-  v[0] = __bfloat162float(*(const __hip_bfloat16*)&t.x);
-  v[1] = __bfloat162float(*(const __hip_bfloat16*)&t.y);
-  v[2] = __bfloat162float(*(const __hip_bfloat16*)&t.z);
-  v[3] = __bfloat162float(*(const __hip_bfloat16*)&t.w);
-}
-
-template <typename T>
-__device__ __forceinline__ void bn_store4(T* p, const float v[4]);
-
-template <>
-__device__ __forceinline__ void bn_store4<float>(float* p, const float v[4]) {
-  *reinterpret_cast<float4*>(p) = float4{v[0], v[1], v[2], v[3]};
-}
-
-template <>
-__device__ __forceinline__ void bn_store4<__hip_bfloat16>(
-    __hip_bfloat16* p, const float v[4]) {
-  ushort4 t;
-  __hip_bfloat16 b;
-  b = __float2bfloat16(v[0]); t.x = *(const unsigned short*)&b;
-  b = __float2bfloat16(v[1]); t.y = *(const unsigned short*)&b;
-  b = __float2bfloat16(v[2]); t.z = *(const unsigned short*)&b;
-  b = __float2bfloat16(v[3]); t.w = *(const unsigned short*)&b;
-  *reinterpret_cast<ushort4*>(p) = t;
-}
-
-constexpr int BN_STRIPES = 16;   // row stripes per block
-constexpr int BN_CG = 64;        // channels per block
 
 // Two per-channel f32 accumulators reduced across a block's stripes:
 // fwd uses (Σx, Σx²); bwd uses (Σdy, Σ dy·x̂).
@@ -102,10 +65,8 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(
     for (int j = 0; j < 4; ++j) {
       mn[j] = smean[c + j];
       iv[j] = sinv[c + j];
-      if (relu) {                    // recompute pre-relu output sign
-        sc[j] = gamma[c + j] * iv[j];
-        sh[j] = beta[c + j] - mn[j] * sc[j];
-      }
+      if (relu)                      // recompute pre-relu output sign
+        bn_scale_shift(gamma[c + j], beta[c + j], mn[j], iv[j], sc[j], sh[j]);
     }
   }
 
@@ -119,16 +80,12 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(
       bn_load4(DY + row * C + c, dy);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (relu && x[j] * sc[j] + sh[j] <= 0.f) continue;  // dy masked by y>0
-        sa[j] += dy[j];
-        sb[j] += dy[j] * (x[j] - mn[j]) * iv[j];
+        if (relu && bn_relu_off(x[j], sc[j], sh[j])) continue;  // dy masked
+        bn_bwd_accum(sa[j], sb[j], dy[j], x[j], mn[j], iv[j]);
       }
     } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        sa[j] += x[j];
-        sb[j] += x[j] * x[j];
-      }
+      for (int j = 0; j < 4; ++j) bn_fwd_accum(sa[j], sb[j], x[j]);
     }
   }
 #pragma unroll
@@ -181,38 +138,30 @@ __global__ __launch_bounds__(256) void bn_finalize_fwd_kernel(
       ta += part_a[(int64_t)s * C + c0 + threadIdx.x];
       tb += part_b[(int64_t)s * C + c0 + threadIdx.x];
     }
-    const float inv_m = 1.f / (float)M;
-    const float mean = ta * inv_m;
-    const float var = fmaxf(tb * inv_m - mean * mean, 0.f);
-    const float inv = rsqrtf(var + eps);
+    float mean, var, inv;
+    bn_fwd_stats(ta, tb, M, eps, mean, var, inv);
     lmean[threadIdx.x] = mean;
     linv[threadIdx.x] = inv;
     if (blockIdx.y == 0) {
       const int gc = c0 + threadIdx.x;
       smean[gc] = mean;
       sinv[gc] = inv;
-      if (rmean != nullptr) {
-        rmean[gc] = (1.f - momentum) * rmean[gc] + momentum * mean;
-        rvar[gc] = (1.f - momentum) * rvar[gc] + momentum * var * unbiased;
-      }
+      if (rmean != nullptr)
+        bn_running_update(rmean[gc], rvar[gc], momentum, mean, var, unbiased);
     }
   }
   __syncthreads();
 
   float scale[4], shift[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    scale[j] = gamma[c + j] * linv[q * 4 + j];
-    shift[j] = beta[c + j] - lmean[q * 4 + j] * scale[j];
-  }
+  for (int j = 0; j < 4; ++j)
+    bn_scale_shift(gamma[c + j], beta[c + j], lmean[q * 4 + j],
+                   linv[q * 4 + j], scale[j], shift[j]);
   for (int64_t row = g; row < M; row += S) {
     float v[4];
     bn_load4(X + row * C + c, v);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[j] = v[j] * scale[j] + shift[j];
-      if (relu) v[j] = fmaxf(v[j], 0.f);
-    }
+    for (int j = 0; j < 4; ++j) v[j] = bn_normalize(v[j], scale[j], shift[j], relu);
     bn_store4(Y + row * C + c, v);
   }
 }
@@ -247,9 +196,7 @@ __global__ __launch_bounds__(256) void bn_finalize_bwd_kernel(
       dgamma[gc] = tdyx;
       dbeta[gc] = tdy;
     }
-    const float inv_m = 1.f / (float)M;
-    lmdy[threadIdx.x] = tdy * inv_m;
-    lmdyx[threadIdx.x] = tdyx * inv_m;
+    bn_bwd_means(tdy, tdyx, M, lmdy[threadIdx.x], lmdyx[threadIdx.x]);
   }
   __syncthreads();
 
@@ -258,39 +205,23 @@ __global__ __launch_bounds__(256) void bn_finalize_bwd_kernel(
   for (int j = 0; j < 4; ++j) {
     mn[j] = smean[c + j];
     iv[j] = sinv[c + j];
-    g_iv[j] = gamma[c + j] * iv[j];
+    bn_scale_shift(gamma[c + j], beta[c + j], mn[j], iv[j], g_iv[j], sh[j]);
     mdy[j] = lmdy[q * 4 + j];
     mdyx[j] = lmdyx[q * 4 + j];
-    if (relu) sh[j] = beta[c + j] - mn[j] * g_iv[j];
   }
   for (int64_t row = g; row < M; row += S) {
     float x[4], dy[4], dx[4];
     bn_load4(X + row * C + c, x);
     bn_load4(DY + row * C + c, dy);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xhat = (x[j] - mn[j]) * iv[j];
-      float d = dy[j];
-      if (relu && x[j] * g_iv[j] + sh[j] <= 0.f) d = 0.f;
-      dx[j] = g_iv[j] * (d - mdy[j] - xhat * mdyx[j]);
-    }
+    for (int j = 0; j < 4; ++j)
+      dx[j] = bn_bwd_dx(x[j], dy[j], mn[j], iv[j], g_iv[j], sh[j], mdy[j],
+                        mdyx[j], relu);
     bn_store4(DX + row * C + c, dx);
   }
 }
 
 // ----------------------------------------------------------------- launch
-static int bn_nslab(int64_t M, int C) {
-  // target ≈256 blocks (one wave over the 8 XCDs); never more slabs than
-  // 16-row stripes available
-  const int cg = C / BN_CG;
-  int ns = 256 / cg;
-  const int max_rows = (int)((M + BN_STRIPES - 1) / BN_STRIPES);
-  if (ns > max_rows) ns = max_rows;
-  if (ns > 64) ns = 64;
-  if (ns < 1) ns = 1;
-  return ns;
-}
-
 extern "C" int flreid_bn_train_nslab(int64_t M, int C) {
   return bn_nslab(M, C);
 }

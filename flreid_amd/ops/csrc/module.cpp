@@ -70,6 +70,9 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(bn_train_nslab);
   FLREID_DEF(bn_train_fwd);
   FLREID_DEF(bn_train_bwd);
+  FLREID_DEF(bn_onepass_config);
+  FLREID_DEF(bn_onepass_fwd);
+  FLREID_DEF(bn_onepass_bwd);
   FLREID_DEF(drift_fwd);
   FLREID_DEF(drift_bwd);
   FLREID_DEF(kd_fwd);

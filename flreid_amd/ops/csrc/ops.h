@@ -163,6 +163,26 @@ void flreid_bn_train_bwd(const void* x, const void* dy, void* dx,
                          float* dbeta, float* part_a, float* part_b, int64_t M,
                          int C, int relu, int dtype, hipStream_t stream);
 
+// ---- bn_onepass.hip -------------------------------------------------------
+// host helper: ≥ 0 when (M, C) is inside the one-launch regime, −1 when the
+// shape stays on the two-launch pair above
+int flreid_bn_onepass_config(int64_t M, int C);
+// bf16 only; same outputs, bit for bit, as flreid_bn_train_fwd / _bwd, with
+// no workspace.  variant < 0 takes the launcher's per-shape tile; otherwise
+// low byte = instantiation, bit 8 = plain block order (benchmark only).
+// Throws when the shape (or the variant) does not fit.
+void flreid_bn_onepass_fwd(const void* x, void* y, const float* gamma,
+                           const float* beta, float* rmean, float* rvar,
+                           float* smean, float* sinv, unsigned long long* nbt,
+                           int64_t M, int C, float momentum, float eps,
+                           float unbiased, int relu, int variant,
+                           hipStream_t stream);
+void flreid_bn_onepass_bwd(const void* x, const void* dy, void* dx,
+                           const float* gamma, const float* beta,
+                           const float* smean, const float* sinv,
+                           float* dgamma, float* dbeta, int64_t M, int C,
+                           int relu, int variant, hipStream_t stream);
+
 // ---- drift.hip ------------------------------------------------------------
 // ptrs: [n][2] int64 (p, anchor); chunks: [n_chunks][4] int32
 // (tensor, elem_offset, len, flat_offset); partials: one float per chunk
