@@ -401,6 +401,26 @@ def bench_bn(results, n):
                     nbytes[d] / (ms / 1e3) / 1e9, 0)
 
 
+def bench_herding(results, n):
+    """K10 selection alone: ops.herding_select on the kernel route
+    (herding.hip, Gram form) against the torch route (the batched
+    expanded-form loop) on the same features, host tables and the final
+    D2H copy included.  (P, n, D, m): the flagship round, a fuller identity,
+    and identities large enough for the workspace path."""
+    for P, rows, D, m in ((64, 8, 2048, 32), (64, 40, 2048, 32),
+                          (16, 300, 2048, 32)):
+        g = torch.Generator().manual_seed(P + rows)
+        feats = torch.relu(torch.randn(P * rows, D, generator=g)).cuda()
+        pids = torch.arange(P).repeat_interleave(rows)[
+            torch.randperm(P * rows, generator=g)]
+        assert ops.herding_route(rows, D, feats.dtype, True) == "kernel"
+        tag = f"herding_p{P}_n{rows}"
+        results[f"{tag}_kernel"] = bench(
+            lambda: ops.herding_select(feats, pids, m), n)
+        results[f"{tag}_torch"] = bench(
+            lambda: ref.herding_select(feats, pids, m), n)
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
@@ -428,11 +448,18 @@ def main():
     p.add_argument("--bn-only", action="store_true",
                    help="run only the train-BN entry: one-launch tiles "
                         "against the two-launch pair")
+    p.add_argument("--herding-only", action="store_true",
+                   help="run only the herding selection entry: kernel "
+                        "against the torch route")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
 
+    if args.herding_only:
+        bench_herding(results, n)
+        report(results)
+        return
     if args.bn_only:
         bench_bn(results, n)
         report(results)

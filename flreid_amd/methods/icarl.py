@@ -107,7 +107,19 @@ class Model(ModelModule):
         imgs, pids = imgs[keep], pids[keep]
         feats = feats[keep.to(feats.device)]
 
-        for person in torch.unique(pids).tolist():
+        # on the GPU every identity is herded by one kernel call (Gram form,
+        # ops.herding_select); elsewhere the per-identity loop below stays
+        counts_max = int(torch.unique(pids, return_counts=True)[1].max()) \
+            if pids.numel() else 0
+        kernel = ops.herding_route(counts_max, feats.shape[1], feats.dtype,
+                                   feats.is_cuda) == "kernel"
+        if kernel:
+            persons, chosen = ops.herding_select(feats, pids, self.m)
+            for person, rows in zip(persons, chosen.tolist()):
+                self.examplars[int(person)] = [
+                    (imgs[j].clone(), int(person)) for j in rows
+                ]
+        for person in ([] if kernel else torch.unique(pids).tolist()):
             sel = (pids == person)
             f = feats[sel.to(feats.device)]
             im = imgs[sel]

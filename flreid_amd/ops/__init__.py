@@ -1910,3 +1910,100 @@ def head_step(rows, partials: torch.Tensor, lr: float, beta1: float,
     ext.head_step(table, partials.data_ptr(), partials.numel(), float(lr),
                   float(beta1), float(beta2), float(weight_decay), float(eps),
                   float(lam), _stream())
+
+
+# ---------------------------------------------------------------------------
+# herding exemplar selection (K10, herding.hip)
+# ---------------------------------------------------------------------------
+
+HERDING_MAX_ROWS = 1024          # largest identity the kernel serves
+HERDING_MAX_WS_BYTES = 256 << 20
+_HERDING_WS_TILE = 64            # herding.hip's workspace Gram tile
+
+
+def herding_route(counts_max: int, d: int, dtype, device_is_cuda: bool) -> str:
+    """Which path serves a herding call whose largest identity has
+    `counts_max` rows of `d` features on the GPU with the extension built:
+    "kernel" (herding.hip) or "torch" (reference.herding_select).
+    FLREID_HERDING=torch forces the torch route."""
+    if (device_is_cuda and dtype == torch.float32 and d >= 4 and d % 4 == 0
+            and 1 <= counts_max <= HERDING_MAX_ROWS
+            and os.environ.get("FLREID_HERDING", "kernel") != "torch"):
+        return "kernel"
+    return "torch"
+
+
+def _herding_tables(counts: Sequence[int], lds_max: int):
+    """(offsets, ws_offsets, tile_rows, ws_floats, n_lds) of identities with
+    `counts` rows, in sorted order: identities above `lds_max` rows get n²
+    workspace floats and one (offset, n, tile row, tile col, ws offset) row
+    per 64×64 tile on or above the diagonal; n_lds is the largest of the
+    others."""
+    offsets, ws_offsets, tile_rows, off, ws, n_lds = [0], [], [], 0, 0, 0
+    for n in counts:
+        if n <= lds_max:
+            ws_offsets.append(0)
+            n_lds = max(n_lds, n)
+        else:
+            ws_offsets.append(ws)
+            nt = -(-n // _HERDING_WS_TILE)
+            tile_rows += [(off, n, bi, bj, ws)
+                          for bi in range(nt) for bj in range(bi, nt)]
+            ws += n * n
+        off += n
+        offsets.append(off)
+    return offsets, ws_offsets, tile_rows, ws, n_lds
+
+
+@torch.no_grad()
+def herding_select(feats: torch.Tensor, pids: torch.Tensor, m: int,
+                   route: Optional[str] = None):
+    """m herding picks per identity, argmin_j ‖μ − (f_j + Σ picked)/(i+1)‖
+    with repeats allowed: (persons, chosen) — the sorted unique ids (a list)
+    and [P, m] int64 original row indices on the CPU.  feats is [N, D] on any
+    device, pids [N] on the CPU, so the partition tables are built on the
+    host with no device sync; the one D2H copy is the result.
+
+    On the GPU the Gram-form kernel serves fp32 features with D % 4 == 0 and
+    identities of up to HERDING_MAX_ROWS rows (Gram workspace of identities
+    above ext.herding_lds_max() rows within HERDING_MAX_WS_BYTES); everything
+    else — and the CPU — runs reference.herding_select.  Where two candidates
+    tie within fp32 rounding the routes may pick differently; route="torch"
+    pins a caller whose results must not move to the reference (None: by
+    `herding_route`)."""
+    if route not in (None, "torch"):
+        raise ValueError(f"herding_select: route {route!r}")
+    if route == "torch" or pids.numel() == 0 or feats.dim() != 2:
+        return ref.herding_select(feats, pids, m)
+    order = torch.argsort(pids, stable=True)
+    persons_t, counts_t = torch.unique_consecutive(pids[order],
+                                                   return_counts=True)
+    counts = counts_t.tolist()
+    if m < 1 or herding_route(max(counts), feats.shape[1], feats.dtype,
+                              feats.is_cuda) != "kernel":
+        return ref.herding_select(feats, pids, m)
+    ext = require_extension("herding_select")
+    if ext is None:
+        return ref.herding_select(feats, pids, m)
+    offsets, ws_offsets, tile_rows, ws_floats, n_lds = _herding_tables(
+        counts, ext.herding_lds_max())
+    if ws_floats * 4 > HERDING_MAX_WS_BYTES:
+        return ref.herding_select(feats, pids, m)
+    dev, P = feats.device, len(counts)
+    f = feats.contiguous()
+    if f.data_ptr() % 16:
+        f = f.clone()
+    # every table in one int32 buffer: one H2D copy
+    sizes = [order.numel(), P + 1, P, 5 * len(tile_rows)]
+    table = torch.cat([
+        order.to(torch.int32),
+        torch.tensor(offsets + ws_offsets, dtype=torch.int32),
+        torch.tensor(tile_rows, dtype=torch.int32).view(-1)]).to(dev)
+    order_d, offsets_d, ws_off_d, tiles_d = table.split(sizes)
+    ws = torch.empty(max(ws_floats, 1), device=dev, dtype=torch.float32)
+    sel = torch.empty(P, m, device=dev, dtype=torch.int32)
+    ext.herding_select(f.data_ptr(), order_d.data_ptr(), offsets_d.data_ptr(),
+                       sel.data_ptr(), ws.data_ptr(), ws_off_d.data_ptr(),
+                       tiles_d.data_ptr(), len(tile_rows), n_lds, P,
+                       f.shape[1], int(m), _stream())
+    return persons_t.tolist(), sel.cpu().to(torch.int64)

@@ -86,6 +86,8 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(penalty_block);
   FLREID_DEF(penalty_fwd);
   FLREID_DEF(penalty_bwd);
+  FLREID_DEF(herding_lds_max);
+  FLREID_DEF(herding_select);
 
   // The three bindings whose Python signature differs from the C one.
 

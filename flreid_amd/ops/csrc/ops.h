@@ -252,6 +252,24 @@ void flreid_penalty_bwd(const int64_t* ptrs, const int* chunks, int S,
                         const float* gscale, float* flat_grad, int n_chunks,
                         hipStream_t stream);
 
+// ---- herding.hip ----------------------------------------------------------
+// host helper: the largest identity (rows) whose Gram matrix stays in LDS
+int flreid_herding_lds_max();
+// Herding exemplar selection, m picks per identity.  feats is [N][D] fp32,
+// 16-byte aligned, D % 4 == 0; order is [N] int32, the rows sorted by
+// identity (stable); offsets is [P + 1] int32 into order; sel is [P][m] int32
+// and receives original row indices.  Identities have 1..1024 rows.  n_lds is
+// the largest identity of at most flreid_herding_lds_max() rows (0: none).
+// Larger identities need gram_ws (n² floats each, at ws_offsets[p] floats;
+// [P] int32, unread for the others) and tiles, n_tiles int32 rows of (offset
+// into order, n, tile row, tile col, ws offset): every 64×64 tile with tile
+// row <= tile col of every such identity.  All tables are device memory.
+void flreid_herding_select(const float* feats, const int* order,
+                           const int* offsets, int* sel, float* gram_ws,
+                           const int* ws_offsets, const int* tiles,
+                           int n_tiles, int n_lds, int P, int D, int m,
+                           hipStream_t stream);
+
 }  // extern "C"
 
 }  // namespace flreid

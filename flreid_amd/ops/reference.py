@@ -408,3 +408,61 @@ def window_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if dropout is not None:
         attn = dropout(attn)
     return attn @ v
+
+
+# ---------------------------------------------------------------------------
+# herding exemplar selection (ref:methods/icarl.py:97-139)
+# ---------------------------------------------------------------------------
+
+def herding_select(feats: torch.Tensor, pids: torch.Tensor, m: int):
+    """m herding picks per identity: (persons, chosen) — the sorted unique
+    ids (a list) and [P, m] int64 original row indices on the CPU.  feats is
+    [N, D] fp32 on any device, pids [N] on the CPU."""
+    # batched sync-free herding: all identities advance together, padded
+    # to the largest per-identity sample count; a handful of kernels per
+    # herding step instead of 4 × n_identities.  The per-identity
+    # partition is built by ONE stable sort (no (pids==p).nonzero loop),
+    # and the argmin uses the expanded form
+    #   ‖μ·(i+1) − acc − f‖² = ‖f‖² − 2⟨f, g_i⟩ + const
+    # so no [P, nmax, D] candidate tensor is ever materialised.
+    dev = feats.device
+    order = torch.argsort(pids, stable=True)                 # cpu
+    persons_t, counts_t = torch.unique_consecutive(
+        pids[order], return_counts=True)
+    persons = persons_t.tolist()
+    P = len(persons)
+    nmax = int(counts_t.max())
+    D = feats.shape[1]
+    offsets = torch.cat([torch.zeros(1, dtype=torch.long),
+                         counts_t.cumsum(0)[:-1]])
+    # position of each (sorted) sample within its identity group
+    pos = torch.arange(pids.numel()) - offsets.repeat_interleave(counts_t)
+    group = torch.arange(P).repeat_interleave(counts_t)
+
+    order_dev = order.to(dev)
+    f_pad = torch.zeros(P, nmax, D, device=dev)
+    f_pad[group.to(dev), pos.to(dev)] = feats.index_select(0, order_dev)
+    pad_penalty = torch.zeros(P, nmax, device=dev)
+    pad_mask = pos.new_zeros(P, nmax, dtype=torch.bool)
+    pad_mask[group, pos] = True
+    pad_penalty.masked_fill_(~pad_mask.to(dev), 1e30)
+    counts = counts_t.to(dev, torch.float32)
+    mu = f_pad.sum(dim=1) / counts.unsqueeze(1)              # [P, D]
+
+    fsq = (f_pad * f_pad).sum(dim=2)                         # [P, nmax]
+    acc = torch.zeros(P, D, device=dev)
+    arange_p = torch.arange(P, device=dev)
+    step_idx = []
+    for i in range(m):
+        g = mu * (i + 1) - acc                               # [P, D]
+        dots = torch.bmm(f_pad, g.unsqueeze(2)).squeeze(2)   # [P, nmax]
+        score = fsq - 2.0 * dots + pad_penalty
+        idx = score.argmin(dim=1)                            # [P]
+        step_idx.append(idx)
+        acc = acc + f_pad[arange_p, idx]
+    sel = torch.stack(step_idx, dim=1).cpu()                 # [P, m]
+
+    # map padded positions back to original sample indices
+    chosen = order.view(-1)[(offsets.unsqueeze(1) + sel).clamp_max(
+        pids.numel() - 1).view(-1)].view(P, -1)
+    return persons, chosen
