@@ -421,6 +421,85 @@ def bench_herding(results, n):
             lambda: ref.herding_select(feats, pids, m), n)
 
 
+def bench_rank_stats(results, n):
+    """K8 evaluation: ops.cmc_map end to end, and the statistics step alone on
+    one [chunk, G] similarity tile, on the kernel route (rank_stats.hip)
+    against the torch route (FLREID_CMC=torch, the argsort / cumsum chain) in
+    one process, the two alternating call by call.  Every call is timed on its
+    own around a synchronise; reported are the median and the min / max over
+    the repetitions.  Shapes (Q, G, D, query_chunk, ids, cameras): the
+    iCaRL-scale gallery, Market-1501's test split, the bench's own split.
+    Features are a unit centre per identity plus noise (same-id cosine ≈ 0.67,
+    others ≈ 0), as a trained model's are: the kernel drops what ranks behind
+    a query's weakest good hit, so its time depends on where the good hits
+    rank — the torch route's does not."""
+    reps = 1 if n == 1 else 7
+
+    def timed(fn, route):
+        if route == "torch":
+            os.environ["FLREID_CMC"] = "torch"
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+        finally:
+            os.environ.pop("FLREID_CMC", None)
+
+    def both(tag, fn):
+        ms = {"kernel": [], "torch": []}
+        for rep in range(reps + 2):                    # two warm-up rounds
+            for route in ms:
+                t = timed(fn, route)
+                if rep >= 2 or reps == 1:
+                    ms[route].append(t)
+        for route, v in ms.items():
+            v.sort()
+            results[f"{tag}_{route}"] = v[len(v) // 2]
+            results[f"{tag}_{route}_min"] = v[0]
+            results[f"{tag}_{route}_max"] = v[-1]
+
+    for Q, G, D, chunk, ids, n_cam in ((2048, 1 << 20, 2048, 256, 50000, 0),
+                                       (3368, 19732, 2048, 2048, 751, 6),
+                                       (128, 256, 2048, 2048, 64, 0)):
+        gen = torch.Generator().manual_seed(G)
+        gl = torch.randint(0, ids, (G,), generator=gen)
+        ql = gl[torch.randperm(G, generator=gen)[:Q]]
+        qc = gc = None
+        if n_cam:
+            gl[torch.randperm(G, generator=gen)[:G // 5]] = -1
+            qc = torch.randint(0, n_cam, (Q,), generator=gen)
+            gc = torch.randint(0, n_cam, (G,), generator=gen)
+        centres = ref.l2_normalize(torch.randn(ids + 1, D, device="cuda"))
+
+        def feats(labels):
+            noise = torch.randn(labels.numel(), D, device="cuda")
+            return ref.l2_normalize(centres[labels.cuda()]
+                                    + noise * (0.7 / D ** 0.5))
+
+        qf, gf = feats(ql), feats(gl)
+        del centres
+        tag = f"cmc_q{Q}_g{G}"
+        both(tag, lambda: ops.cmc_map(qf, ql, gf, gl, qc, gc,
+                                      query_chunk=chunk))
+        # the statistics step alone, on the first chunk's tile
+        c = min(Q, chunk)
+        sims = ops.similarity_matrix(qf[:c], gf)
+        tables = ops.rank_stats_tables(ql, gl, qc, gc, "cuda").rows(0, c)
+        assert ops.cmc_map_route(Q, G, tables.max_good, True) == "kernel"
+        qlc, qcc = ql[:c], qc[:c] if qc is not None else None
+
+        def stats():
+            if os.environ.get("FLREID_CMC") == "torch":
+                return ref.cmc_map_from_sims(sims, qlc, gl, qcc, gc)
+            return ops.rank_stats_from_sims(sims, qlc, gl, qcc, gc,
+                                            tables=tables)
+
+        both(f"{tag}_stats{c}", stats)
+        del qf, gf, sims
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
@@ -451,11 +530,18 @@ def main():
     p.add_argument("--herding-only", action="store_true",
                    help="run only the herding selection entry: kernel "
                         "against the torch route")
+    p.add_argument("--rank-stats-only", action="store_true",
+                   help="run only the CMC/mAP entry: rank-statistics kernel "
+                        "against the torch sort chain")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
 
+    if args.rank_stats_only:
+        bench_rank_stats(results, n)
+        report(results)
+        return
     if args.herding_only:
         bench_herding(results, n)
         report(results)

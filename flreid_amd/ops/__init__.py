@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import os
 from collections import OrderedDict
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -544,19 +544,152 @@ def triplet_loss(feature: torch.Tensor, target: torch.Tensor,
     return ref.triplet_loss(feature, target, margin, norm_feat, hard_mining)
 
 
+def rank_stats_max_good() -> int:
+    """The largest same-id group (good entries of one query) rank_stats.hip
+    serves; −1 (no group fits) without the extension under
+    FLREID_ALLOW_EAGER=1."""
+    ext = require_extension("rank_stats")
+    return ext.rank_stats_max_good() if ext is not None else -1
+
+
+def cmc_map_route(q: int, g: int, max_good: int, device_is_cuda: bool) -> str:
+    """Which path turns the similarities of `q` queries against `g` gallery
+    entries, the largest same-id group `max_good` entries, into CMC / mAP:
+    "kernel" (rank_stats.hip, no sort) or "torch" (the argsort / cumsum chain
+    of reference.cmc_map_from_sims).  FLREID_CMC=torch forces the torch
+    route."""
+    if (device_is_cuda and q >= 1 and g >= 1
+            and os.environ.get("FLREID_CMC", "kernel") != "torch"
+            and max_good <= rank_stats_max_good()):
+        return "kernel"
+    return "torch"
+
+
+class RankTables(NamedTuple):
+    """What rank_stats.hip reads besides the similarities, built once per
+    evaluation: `perm` [G] int32, the gallery sorted by label; `segs` [Q, 2]
+    int32, each query's same-id segment [lo, hi) of perm; `neg` [2] int32,
+    the segment of the label −1; `qcam` [Q] / `gcam` [G] int32 (both None
+    without cameras); `max_good`, the longest segment."""
+    perm: torch.Tensor
+    segs: torch.Tensor
+    neg: torch.Tensor
+    qcam: Optional[torch.Tensor]
+    gcam: Optional[torch.Tensor]
+    max_good: int
+
+    def rows(self, s0: int, s1: int) -> "RankTables":
+        """The tables of queries s0..s1 (a query chunk)."""
+        return self._replace(
+            segs=self.segs[s0:s1],
+            qcam=self.qcam[s0:s1] if self.qcam is not None else None)
+
+
+@torch.no_grad()
+def rank_stats_tables(query_labels, gallery_labels, query_camera_labels=None,
+                      gallery_camera_labels=None, device=None) -> RankTables:
+    """RankTables of an evaluation, by device-side torch ops (one sort of the
+    gallery labels, two searchsorted) and one sync for `max_good`.  Camera
+    ids are compared as int32."""
+    ql = query_labels.to(device, torch.int64).view(-1)
+    gl = gallery_labels.to(device, torch.int64).view(-1)
+    cams = query_camera_labels is not None and gallery_camera_labels is not None
+    gl_sorted, perm = torch.sort(gl)
+    lo = torch.searchsorted(gl_sorted, ql)
+    hi = torch.searchsorted(gl_sorted, ql, right=True)
+    if cams:
+        # a −1 query has no good entry, and its same-id segment is the −1
+        # segment, which is junk already
+        hi = torch.where(ql == -1, lo, hi)
+        minus1 = torch.full((1,), -1, dtype=torch.int64, device=gl.device)
+        neg = torch.cat([torch.searchsorted(gl_sorted, minus1),
+                         torch.searchsorted(gl_sorted, minus1, right=True)])
+    else:
+        neg = torch.zeros(2, dtype=torch.int64, device=gl.device)
+    return RankTables(
+        perm.to(torch.int32), torch.stack([lo, hi], dim=1).to(torch.int32),
+        neg.to(torch.int32),
+        query_camera_labels.to(device, torch.int32).view(-1) if cams else None,
+        gallery_camera_labels.to(device, torch.int32).view(-1) if cams else None,
+        int((hi - lo).max()) if ql.numel() else 0)
+
+
+def _rank_stats_gpu(ext, sims: torch.Tensor, t: RankTables):
+    sims = sims.contiguous().float()
+    qc, g = sims.shape
+    dev = sims.device
+    ws = torch.empty(ext.rank_stats_ws_ints(qc, g, t.max_good), device=dev,
+                     dtype=torch.int32)
+    first_rank = torch.empty(qc, device=dev, dtype=torch.int32)
+    n_good = torch.empty(qc, device=dev, dtype=torch.int32)
+    ap = torch.empty(qc, device=dev, dtype=torch.float64)
+    ext.rank_stats(sims.data_ptr(), t.perm.data_ptr(),
+                   t.segs.contiguous().data_ptr(), t.neg.data_ptr(),
+                   t.qcam.contiguous().data_ptr() if t.qcam is not None else 0,
+                   t.gcam.data_ptr() if t.gcam is not None else 0,
+                   ws.data_ptr(), first_rank.data_ptr(), n_good.data_ptr(),
+                   ap.data_ptr(), qc, g, t.max_good, _stream())
+    return first_rank.long(), n_good.long(), ap
+
+
+@torch.no_grad()
+def rank_stats_from_sims(sims, query_labels, gallery_labels,
+                         query_camera_labels=None, gallery_camera_labels=None,
+                         tables: Optional[RankTables] = None):
+    """(first_rank, n_good, ap) of every row of sims [Qc, G] — int64, int64,
+    float64 on sims' device: the junk-free 0-based rank of the query's first
+    good hit (−1 without one), its number of good entries and its average
+    precision, with the semantics of reference.cmc_map_from_sims.  On the GPU
+    rank_stats.hip computes them without sorting the rows; `tables` (the rows
+    of this chunk, `RankTables.rows`) spares rebuilding them per chunk.  The
+    CPU, FLREID_CMC=torch and groups above `rank_stats_max_good()` take
+    reference.rank_stats_from_sims."""
+    if sims.is_cuda and sims.numel() > 0:
+        if tables is None:
+            tables = rank_stats_tables(query_labels, gallery_labels,
+                                       query_camera_labels,
+                                       gallery_camera_labels, sims.device)
+        if cmc_map_route(sims.shape[0], sims.shape[1], tables.max_good,
+                         True) == "kernel":
+            return _rank_stats_gpu(require_extension("rank_stats"), sims,
+                                   tables)
+    return ref.rank_stats_from_sims(sims, query_labels, gallery_labels,
+                                    query_camera_labels, gallery_camera_labels)
+
+
 def cmc_map(query_features, query_labels, gallery_features, gallery_labels,
             query_camera_labels=None, gallery_camera_labels=None,
             query_chunk: int = 2048):
-    """On GPU the Q×G similarity runs on the MFMA pairwise kernel; the rank
-    statistics stay in device-side torch ops.  Queries are processed in
-    chunks so million-image galleries (iCaRL config — K8/288 GB HBM) never
-    materialise more than [chunk, G] similarities at once."""
+    """On GPU the Q×G similarity runs on the MFMA pairwise kernel and the rank
+    statistics on rank_stats.hip (`cmc_map_route`; the torch route keeps them
+    in device-side torch ops).  Queries are processed in chunks so
+    million-image galleries (iCaRL config — K8/288 GB HBM) never materialise
+    more than [chunk, G] similarities at once."""
     if not query_features.is_cuda:
         return ref.cmc_map(query_features, query_labels, gallery_features,
                            gallery_labels, query_camera_labels,
                            gallery_camera_labels)
     q = query_features.shape[0]
     g = gallery_features.shape[0]
+    if cmc_map_route(q, g, 0, True) == "kernel":
+        tables = rank_stats_tables(query_labels, gallery_labels,
+                                   query_camera_labels, gallery_camera_labels,
+                                   query_features.device)
+        if cmc_map_route(q, g, tables.max_good, True) == "kernel":
+            ext = require_extension("rank_stats")
+            stats = []
+            for s0 in range(0, q, query_chunk):
+                s1 = min(q, s0 + query_chunk)
+                sims = similarity_matrix(query_features[s0:s1],
+                                         gallery_features)
+                stats.append(_rank_stats_gpu(ext, sims, tables.rows(s0, s1)))
+            first_rank, n_good, ap = (torch.cat(x) for x in zip(*stats))
+            hist = torch.bincount(first_rank[n_good > 0], minlength=g + 1)
+            # divided on the host: the device divides a tensor by a python
+            # scalar as a product with its reciprocal, a last bit away from
+            # the CPU reference
+            cmc = hist[:g].to(torch.float64).cumsum(0).cpu() / q
+            return cmc, float(ap.sum().item() / q)
     if q <= query_chunk:
         sims = similarity_matrix(query_features, gallery_features)
         return ref.cmc_map_from_sims(sims, query_labels, gallery_labels,

@@ -88,6 +88,9 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(penalty_bwd);
   FLREID_DEF(herding_lds_max);
   FLREID_DEF(herding_select);
+  FLREID_DEF(rank_stats_max_good);
+  FLREID_DEF(rank_stats_ws_ints);
+  FLREID_DEF(rank_stats);
 
   // The three bindings whose Python signature differs from the C one.
 

@@ -270,6 +270,26 @@ void flreid_herding_select(const float* feats, const int* order,
                            int n_tiles, int n_lds, int P, int D, int m,
                            hipStream_t stream);
 
+// ---- rank_stats.hip -------------------------------------------------------
+// host helper: the most good entries (same-id group size) one query may have
+int flreid_rank_stats_max_good();
+// host helper: int32 elements of workspace a [Qc, G] tile needs when no
+// query's same-id segment exceeds kmax
+int64_t flreid_rank_stats_ws_ints(int64_t Qc, int64_t G, int kmax);
+// CMC / AP rank statistics of sims [Qc][G] fp32 (contiguous, any 4-byte
+// alignment), without sorting the rows.  perm is [G] int32, the gallery
+// sorted by label; segs is [Qc][2] int32, each query's same-id segment
+// [lo, hi) of perm, at most kmax long; neg is [2] int32, the segment of the
+// label −1.  qcam [Qc] / gcam [G] int32 are both given (camera mode: same-id
+// same-camera entries and the −1 segment are junk) or both null (nothing is
+// junk, neg unread).  Outputs per row: first_rank, the junk-free 0-based rank
+// of the first good hit (−1 without one), n_good and ap.  ws is uninitialised
+// scratch of flreid_rank_stats_ws_ints(Qc, G, kmax) int32.
+void flreid_rank_stats(const float* sims, const int* perm, const int* segs,
+                       const int* neg, const int* qcam, const int* gcam,
+                       int* ws, int* first_rank, int* n_good, double* ap,
+                       int64_t Qc, int64_t G, int kmax, hipStream_t stream);
+
 }  // extern "C"
 
 }  // namespace flreid

@@ -385,6 +385,56 @@ def cmc_map_from_sims(sims: torch.Tensor, query_labels: torch.Tensor,
     return cmc.cpu(), float(ap.sum().item() / q)
 
 
+@torch.no_grad()
+def rank_stats_from_sims(sims: torch.Tensor, query_labels: torch.Tensor,
+                         gallery_labels: torch.Tensor,
+                         query_camera_labels: Optional[torch.Tensor] = None,
+                         gallery_camera_labels: Optional[torch.Tensor] = None,
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(first_rank, n_good, ap) per query — int64, int64, float64 — written
+    from the definition, with no sort of the row: a good entry's junk-free
+    rank is the number of valid entries ranking ahead of it, where entry j
+    ranks ahead of entry p iff sim_j > sim_p, or sim_j == sim_p and j > p.
+    first_rank is −1 and ap 0 for a query without a good entry."""
+    q, g = sims.shape
+    device = sims.device
+    ql = query_labels.to(device).view(q)
+    gl = gallery_labels.to(device).view(g)
+    cams = query_camera_labels is not None and gallery_camera_labels is not None
+    if cams:
+        qc = query_camera_labels.to(device).view(q)
+        gc = gallery_camera_labels.to(device).view(g)
+    idx = torch.arange(g, device=device)
+    first_rank = torch.full((q,), -1, dtype=torch.int64, device=device)
+    n_good = torch.zeros(q, dtype=torch.int64, device=device)
+    ap = torch.zeros(q, dtype=torch.float64, device=device)
+    for i in range(q):
+        s = sims[i]
+        same_id = gl == ql[i]
+        if cams:
+            same_cam = gc == qc[i]
+            valid = ~((gl == -1) | (same_id & same_cam))
+            good = same_id & ~same_cam & (gl != -1)
+        else:
+            valid = torch.ones_like(same_id)
+            good = same_id
+        gi = good.nonzero().view(-1)
+        n = gi.numel()
+        if n == 0:
+            continue
+        sg = s[gi].view(n, 1)
+        ahead = (s.view(1, g) > sg) | ((s.view(1, g) == sg)
+                                       & (idx.view(1, g) > gi.view(n, 1)))
+        r = (ahead & valid.view(1, g)).sum(dim=1).sort()[0].to(torch.float64)
+        p = torch.arange(n, device=device, dtype=torch.float64)
+        old_precision = torch.where(r > 0, p / r.clamp(min=1),
+                                    torch.ones_like(r))
+        first_rank[i] = int(r[0])
+        n_good[i] = n
+        ap[i] = (((p + 1.0) / (r + 1.0) + old_precision) * 0.5).sum() / n
+    return first_rank, n_good, ap
+
+
 # ---------------------------------------------------------------------------
 # Swin window attention (ref:models/swin_transformer.py:255-286)
 # ---------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 The reference loops over queries in python, doing a GEMV + np.argsort per
 query (ref:tools/evaluate.py:103-142).  Here the whole evaluation is one
 batched Q×G similarity GEMM + a vectorised rank reduction (ops.cmc_map),
-which runs on-device (MI355X: MFMA GEMM + device sort) or on CPU.
+which runs on-device (MI355X: MFMA GEMM + sort-free rank statistics) or on CPU.
 """
 
 from __future__ import annotations
