@@ -400,6 +400,102 @@ def bench_bn(results, n):
                 results[f"{tag}_{d}_{name}_GBps"] = round(
                     nbytes[d] / (ms / 1e3) / 1e9, 0)
 
+    bench_bn_residual(results, timed)
+
+
+def bench_bn_residual(results, timed):
+    """relu(bn(x) + identity) from the BN kernel against the three-kernel
+    chain (bn, add, ReLU / threshold_backward) it replaces: train forward and
+    backward at 2048×2048 bf16, and the eval pass (16-byte kernel with the
+    residual against the one-element kernel + add + ReLU) on a
+    [512, 256, 32, 16] channels-last capture chunk.  *_GBps = the bytes the
+    fused form must move over its time."""
+    ext = ops.require_extension("bn bench")
+    st = torch.cuda.current_stream().cuda_stream
+    f32 = dict(device="cuda", dtype=torch.float32)
+
+    m, c = 2048, 2048
+    x, res, dz = (torch.randn(m, c, device="cuda").bfloat16()
+                  for _ in range(3))
+    y, z, dx, dres = (torch.empty_like(x) for _ in range(4))
+    gamma, beta = torch.rand(c, **f32) + 0.5, torch.randn(c, **f32)
+    rm, rv = torch.zeros(c, **f32), torch.ones(c, **f32)
+    sm, si = torch.empty(c, **f32), torch.empty(c, **f32)
+    dg, db = torch.empty(c, **f32), torch.empty(c, **f32)
+    nbt = torch.zeros((), device="cuda", dtype=torch.long)
+    unb = m / (m - 1)
+    ptr = lambda *ts: [t.data_ptr() for t in ts]          # noqa: E731
+    px, pres, pdz, py, pz, pdx, pdres = ptr(x, res, dz, y, z, dx, dres)
+    pg, pb, prm, prv, psm, psi, pdg, pdb = ptr(gamma, beta, rm, rv, sm, si,
+                                               dg, db)
+    pn = nbt.data_ptr()
+
+    def fwd_fused():
+        ext.bn_onepass_res_fwd(px, pres, pz, pg, pb, prm, prv, psm, psi, pn,
+                               m, c, 0.1, 1e-5, unb, -1, st)
+
+    def fwd_chain():
+        ext.bn_onepass_fwd(px, py, pg, pb, prm, prv, psm, psi, pn, m, c, 0.1,
+                           1e-5, unb, 0, -1, st)
+        torch.relu_(y + res)
+
+    fwd_fused()                     # z for the two backward rows
+
+    def bwd_fused():
+        ext.bn_onepass_res_bwd(px, pdz, pz, pdres, pdx, pg, pb, psm, psi, pdg,
+                               pdb, m, c, -1, st)
+
+    def bwd_chain():
+        d = torch.ops.aten.threshold_backward(dz, z, 0)
+        ext.bn_onepass_bwd(px, d.data_ptr(), pdx, pg, pb, psm, psi, pdg, pdb,
+                           m, c, 0, -1, st)
+
+    el = m * c * 2
+    for name, fn, nbytes in (("fwd_fused", fwd_fused, 3 * el),
+                             ("fwd_chain", fwd_chain, 3 * el),
+                             ("bwd_fused", bwd_fused, 5 * el),
+                             ("bwd_chain", bwd_chain, 5 * el)):
+        ms = timed(fn)
+        results[f"bn_res_m{m}_c{c}_{name}"] = ms
+        results[f"bn_res_m{m}_c{c}_{name}_GBps"] = round(
+            nbytes / (ms / 1e3) / 1e9, 0)
+
+    shape = (512, 256, 32, 16)
+    xe, re_ = (torch.randn(shape, device="cuda").bfloat16().to(
+        memory_format=torch.channels_last) for _ in range(2))
+    ye = torch.empty_like(xe)
+    ce = shape[1]
+    ge, be = torch.rand(ce, **f32) + 0.5, torch.randn(ce, **f32)
+    me, ve = torch.randn(ce, **f32), torch.rand(ce, **f32) + 0.5
+    pxe, pre, pye, pge, pbe, pme, pve = ptr(xe, re_, ye, ge, be, me, ve)
+    n_el, hw = xe.numel(), shape[2] * shape[3]
+
+    def eval_fused():
+        ext.bn_eval_res(pxe, pre, pye, pge, pbe, pme, pve, n_el, ce, hw, 1e-5,
+                        1, 0, 1, 1, st)
+
+    def eval_chain():
+        ext.bn_eval_res(pxe, 0, pye, pge, pbe, pme, pve, n_el, ce, hw, 1e-5,
+                        1, 0, 0, 1, st)
+        torch.relu_(ye + re_)
+
+    def eval_wide():
+        ext.bn_eval_res(pxe, 0, pye, pge, pbe, pme, pve, n_el, ce, hw, 1e-5,
+                        1, 1, 1, 1, st)
+
+    def eval_scalar():
+        ext.bn_eval_res(pxe, 0, pye, pge, pbe, pme, pve, n_el, ce, hw, 1e-5,
+                        1, 1, 0, 1, st)
+
+    for name, fn, nbytes in (("fused", eval_fused, 3 * n_el * 2),
+                             ("chain", eval_chain, 3 * n_el * 2),
+                             ("wide_noresidual", eval_wide, 2 * n_el * 2),
+                             ("scalar_noresidual", eval_scalar, 2 * n_el * 2)):
+        ms = timed(fn)
+        results[f"bn_eval_res_{name}"] = ms
+        results[f"bn_eval_res_{name}_GBps"] = round(
+            nbytes / (ms / 1e3) / 1e9, 0)
+
 
 def bench_herding(results, n):
     """K10 selection alone: ops.herding_select on the kernel route

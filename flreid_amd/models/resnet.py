@@ -42,11 +42,19 @@ class EvalFusedBatchNorm2d(nn.BatchNorm2d):
     When `fuse_relu` is set (bn1/bn2 inside the residual blocks and the stem
     BN — everywhere the model applies BN→ReLU directly) the ReLU runs inside
     the same kernels; the torch fallback applies it explicitly so CPU
-    semantics are identical.  CPU and out-of-regime shapes fall through."""
+    semantics are identical.  A block's last BN takes the identity as
+    `residual` and folds the add and the ReLU in as well where the kernels
+    allow it.  CPU and out-of-regime shapes fall through."""
 
     fuse_relu = False
 
-    def forward(self, x):
+    def forward(self, x, residual=None):
+        """With `residual` (a block's identity) the result is
+        relu(bn(x) + residual) from the BN kernel itself, or None when that
+        route does not apply — the caller then runs the plain sequence."""
+        if residual is not None:
+            fused = ops.bn_eval_2d if not self.training else ops.bn_train_2d
+            return fused(x, self, residual=residual)
         if not self.training:
             out = ops.bn_eval_2d(x, self, relu=self.fuse_relu)
             if out is not None:
@@ -57,6 +65,14 @@ class EvalFusedBatchNorm2d(nn.BatchNorm2d):
                 return out
         out = super().forward(x)
         return F.relu(out, inplace=True) if self.fuse_relu else out
+
+
+def _bn_add_relu(bn: nn.Module, x: torch.Tensor, identity: torch.Tensor):
+    """relu(bn(x) + identity) from the BN kernel, or None (a swapped-in norm
+    layer, CPU, a shape or layout the kernels do not take)."""
+    if isinstance(bn, EvalFusedBatchNorm2d):
+        return bn(x, residual=identity)
+    return None
 
 
 class EvalFusedBatchNorm1d(nn.BatchNorm1d):
@@ -114,8 +130,11 @@ class BasicBlock(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         identity = x if self.downsample is None else self.downsample(x)
         out = self.bn1(self.conv1(x))          # ReLU fused into bn1
-        out = self.bn2(self.conv2(out))
-        return self.relu(out + identity)
+        out = self.conv2(out)
+        fused = _bn_add_relu(self.bn2, out, identity)
+        if fused is not None:
+            return fused
+        return self.relu(self.bn2(out) + identity)
 
 
 class Bottleneck(nn.Module):
@@ -139,8 +158,11 @@ class Bottleneck(nn.Module):
         identity = x if self.downsample is None else self.downsample(x)
         out = self.bn1(self.conv1(x))          # ReLU fused into bn1/bn2
         out = self.bn2(self.conv2(out))
-        out = self.bn3(self.conv3(out))
-        return self.relu(out + identity)
+        out = self.conv3(out)
+        fused = _bn_add_relu(self.bn3, out, identity)
+        if fused is not None:
+            return fused
+        return self.relu(self.bn3(out) + identity)
 
 
 class ResNetTrunk(nn.Module):

@@ -1157,14 +1157,41 @@ def adaptive_linear_fwd(x: torch.Tensor, gw: torch.Tensor,
     return out
 
 
-def bn_eval_2d(x: torch.Tensor, bn, relu: bool = False) -> Optional[torch.Tensor]:
+def bn_residual_enabled() -> bool:
+    """FLREID_BN_RESIDUAL=0 keeps relu(bn(x) + identity) on the three-kernel
+    sequence (same bits; A/B lever)."""
+    return os.environ.get("FLREID_BN_RESIDUAL", "1") != "0"
+
+
+def _residual_matches(x: torch.Tensor, residual: torch.Tensor) -> bool:
+    return (residual.is_cuda and residual.device == x.device
+            and residual.dtype == x.dtype and residual.shape == x.shape
+            and residual.stride() == x.stride())
+
+
+def bn_eval_2d(x: torch.Tensor, bn, relu: bool = False,
+               residual: Optional[torch.Tensor] = None,
+               ) -> Optional[torch.Tensor]:
     """Fused eval-mode BatchNorm2d (one coalesced pass; MIOpen's inference
-    kernel measured ~0.3 TB/s on ReID shapes).  Returns None when the fused
-    path does not apply (train mode, CPU, missing stats/extension)."""
+    kernel measured ~0.3 TB/s on ReID shapes).  With `residual` the same pass
+    returns relu(bn(x) + residual), bit for bit what the separate add and
+    ReLU give.  Returns None when the fused path does not apply (train mode,
+    CPU, missing stats/extension; with a residual also a residual of another
+    layout, dtype or shape or one that requires grad, and
+    FLREID_BN_RESIDUAL=0)."""
     if (not x.is_cuda or x.requires_grad or bn.running_mean is None
             or x.dtype not in (torch.float32, torch.bfloat16)
             or x.dim() not in (2, 4)):
         return None
+    if residual is not None:
+        if relu:
+            raise ValueError("bn_eval_2d: a residual implies the ReLU")
+        if (not bn_residual_enabled() or residual.requires_grad
+                or not _residual_matches(x, residual)):
+            return None
+        if not (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(
+                memory_format=torch.channels_last))):
+            return None
     ext = _load_extension()
     if ext is None:
         return None
@@ -1179,13 +1206,21 @@ def bn_eval_2d(x: torch.Tensor, bn, relu: bool = False) -> Optional[torch.Tensor
         hw = x.shape[2] * x.shape[3]
     out = torch.empty_like(x)
     c = x.shape[1]
-    ext.bn_eval(x.data_ptr(), out.data_ptr(),
-                bn.weight.detach().float().contiguous().data_ptr(),
-                bn.bias.detach().float().contiguous().data_ptr(),
-                bn.running_mean.float().contiguous().data_ptr(),
-                bn.running_var.float().contiguous().data_ptr(),
-                x.numel(), c, hw, float(bn.eps), int(nhwc), int(relu),
-                _dt(x), _stream())
+    # the temporaries must outlive the launch call
+    gamma = bn.weight.detach().float().contiguous()
+    beta = bn.bias.detach().float().contiguous()
+    mean = bn.running_mean.float().contiguous()
+    var = bn.running_var.float().contiguous()
+    if residual is None:
+        ext.bn_eval(x.data_ptr(), out.data_ptr(), gamma.data_ptr(),
+                    beta.data_ptr(), mean.data_ptr(), var.data_ptr(),
+                    x.numel(), c, hw, float(bn.eps), int(nhwc), int(relu),
+                    _dt(x), _stream())
+    else:
+        ext.bn_eval_res(x.data_ptr(), residual.data_ptr(), out.data_ptr(),
+                        gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
+                        var.data_ptr(), x.numel(), c, hw, float(bn.eps),
+                        int(nhwc), 0, 1, _dt(x), _stream())
     return out
 
 
@@ -1413,7 +1448,7 @@ class _BnTrain2dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps,
-                nbt, relu, onepass):
+                nbt, relu, onepass, residual=None):
         ext = require_extension("bn_train")
         c = x.shape[1]
         m = x.numel() // c
@@ -1423,6 +1458,24 @@ class _BnTrain2dFn(torch.autograd.Function):
         has_rs = running_mean is not None
         ctx.relu = bool(relu)
         ctx.onepass = bool(onepass)
+        ctx.residual = residual is not None
+        if residual is not None:
+            # y = relu(bn(x) + residual) in the one launch; backward needs y
+            if relu or not onepass:
+                raise ValueError("bn_train: the residual epilogue is one-launch"
+                                 " only and implies the ReLU")
+            ext.bn_onepass_res_fwd(
+                x.data_ptr(), residual.data_ptr(), y.data_ptr(),
+                gamma.detach().contiguous().data_ptr(),
+                beta.detach().contiguous().data_ptr(),
+                running_mean.data_ptr() if has_rs else 0,
+                running_var.data_ptr() if has_rs else 0,
+                smean.data_ptr(), sinv.data_ptr(),
+                nbt.data_ptr() if nbt is not None else 0, m, c,
+                float(momentum), float(eps), float(m) / float(m - 1),
+                -1, _stream())
+            ctx.save_for_backward(x, gamma, beta, smean, sinv, y)
+            return y
         if onepass:
             ext.bn_onepass_fwd(
                 x.data_ptr(), y.data_ptr(),
@@ -1456,7 +1509,7 @@ class _BnTrain2dFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, gamma, beta, smean, sinv = ctx.saved_tensors
+        x, gamma, beta, smean, sinv = ctx.saved_tensors[:5]
         if x.dim() == 4:
             if not dy.is_contiguous(memory_format=torch.channels_last):
                 dy = dy.contiguous(memory_format=torch.channels_last)
@@ -1470,6 +1523,18 @@ class _BnTrain2dFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgamma = torch.empty(c, device=x.device, dtype=torch.float32)
         dbeta = torch.empty(c, device=x.device, dtype=torch.float32)
+        if ctx.residual:
+            z = ctx.saved_tensors[5]
+            dres = torch.empty_like(x) if ctx.needs_input_grad[10] else None
+            ext.bn_onepass_res_bwd(
+                x.data_ptr(), dy.data_ptr(), z.data_ptr(),
+                dres.data_ptr() if dres is not None else 0, dx.data_ptr(),
+                gamma.detach().contiguous().data_ptr(),
+                beta.detach().contiguous().data_ptr(),
+                smean.data_ptr(), sinv.data_ptr(),
+                dgamma.data_ptr(), dbeta.data_ptr(), m, c, -1, _stream())
+            return (dx, dgamma, dbeta, None, None, None, None, None, None,
+                    None, dres)
         if ctx.onepass:
             ext.bn_onepass_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(),
                                gamma.detach().contiguous().data_ptr(),
@@ -1477,7 +1542,8 @@ class _BnTrain2dFn(torch.autograd.Function):
                                smean.data_ptr(), sinv.data_ptr(),
                                dgamma.data_ptr(), dbeta.data_ptr(),
                                m, c, int(ctx.relu), -1, _stream())
-            return dx, dgamma, dbeta, None, None, None, None, None, None, None
+            return (dx, dgamma, dbeta, None, None, None, None, None, None,
+                    None, None)
         nslab = ext.bn_train_nslab(m, c)
         part = torch.empty(2, nslab, c, device=x.device, dtype=torch.float32)
         ext.bn_train_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(),
@@ -1487,7 +1553,8 @@ class _BnTrain2dFn(torch.autograd.Function):
                          dgamma.data_ptr(), dbeta.data_ptr(),
                          part[0].data_ptr(), part[1].data_ptr(),
                          m, c, int(ctx.relu), _dt(x), _stream())
-        return dx, dgamma, dbeta, None, None, None, None, None, None, None
+        return (dx, dgamma, dbeta, None, None, None, None, None, None, None,
+                None)
 
 
 def bn_onepass_applies(m: int, c: int, dtype: torch.dtype) -> bool:
@@ -1503,8 +1570,9 @@ def bn_onepass_applies(m: int, c: int, dtype: torch.dtype) -> bool:
     return ext is not None and ext.bn_onepass_config(m, c) >= 0
 
 
-def bn_train_2d(x: torch.Tensor, bn,
-                relu: bool = False) -> Optional[torch.Tensor]:
+def bn_train_2d(x: torch.Tensor, bn, relu: bool = False,
+                residual: Optional[torch.Tensor] = None,
+                ) -> Optional[torch.Tensor]:
     """Fused TRAINING-mode BatchNorm for the head-epoch regime.  Applies to
     CUDA channels-last 4-D tensors (BatchNorm2d) and contiguous 2-D tensors
     (BatchNorm1d — the BNNeck bottleneck) with C % 64 == 0 and a small row
@@ -1513,10 +1581,20 @@ def bn_train_2d(x: torch.Tensor, bn,
     stays on MIOpen's multi-block reduction).  The
     num_batches_tracked increment is fused into the forward kernel.  Inside
     that window bn_onepass_applies() picks the one-launch kernels over the
-    two-launch pair (FLREID_BN_ONEPASS=0 forces the pair).  Returns None
-    when the fused path does not apply."""
+    two-launch pair (FLREID_BN_ONEPASS=0 forces the pair).  With `residual`
+    (the block's identity: x's shape, layout and dtype) the one-launch
+    kernels return relu(bn(x) + residual) and hand the residual its gradient,
+    bit for bit what the separate add, ReLU and threshold_backward give; that
+    route exists only inside bn_onepass_applies() and FLREID_BN_RESIDUAL=0
+    switches it off.  Returns None when the fused path does not apply."""
     if os.environ.get("FLREID_NO_FUSED_BN", "0") == "1":
         return None
+    if residual is not None:
+        if relu:
+            raise ValueError("bn_train_2d: a residual implies the ReLU")
+        if (not bn_residual_enabled() or not x.is_cuda
+                or not _residual_matches(x, residual)):
+            return None
     if (not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16)
             or bn.weight is None or bn.bias is None):
         return None
@@ -1542,9 +1620,14 @@ def bn_train_2d(x: torch.Tensor, bn,
         rm, rv = bn.running_mean, bn.running_var
     else:
         rm = rv = None
-    return _BnTrain2dFn.apply(x, bn.weight, bn.bias, rm, rv,
-                              bn.momentum, bn.eps, nbt, relu,
-                              bn_onepass_applies(m, c, x.dtype))
+    onepass = bn_onepass_applies(m, c, x.dtype)
+    if residual is None:
+        return _BnTrain2dFn.apply(x, bn.weight, bn.bias, rm, rv,
+                                  bn.momentum, bn.eps, nbt, relu, onepass)
+    if not onepass:
+        return None
+    return _BnTrain2dFn.apply(x, bn.weight, bn.bias, rm, rv, bn.momentum,
+                              bn.eps, nbt, False, True, residual)
 
 
 def _cl(t: torch.Tensor) -> torch.Tensor:

@@ -21,6 +21,13 @@
 // Blocks never wait for each other.  All arithmetic comes from bn_train.h,
 // the text the two-launch kernels compile from.
 //
+// Residual epilogue (RESID instantiations): a block's last BatchNorm is
+// followed by relu(y + identity).  Forward reads the identity's quad in step 5
+// and stores relu(bf16(y) + res) — the bits of the add and clamp kernels it
+// replaces; statistics are untouched.  Backward masks dy with the saved
+// output z as it loads it (threshold_backward), stores the masked value as
+// the identity's gradient, and runs the plain backward on it.
+//
 // Thread mapping <QUADS, P, SPT, RPS>: thread = (row-thread p, quad q), P
 // row-threads; row-thread p owns stripes p, p+P, … (SPT of them) and up to
 // RPS rows of each, so a shape fits when SPT·P ≥ S and RPS ≥ ceil(M/S).
@@ -87,9 +94,10 @@ __device__ __forceinline__ void bn_op_reduce(const float* la, const float* lb,
 }
 
 // ---------------------------------------------------------------- forward
-template <int QUADS, int P, int SPT, int RPS>
+template <int QUADS, int P, int SPT, int RPS, bool RESID>
 __global__ __launch_bounds__(QUADS* P) void bn_onepass_fwd_kernel(
-    const __hip_bfloat16* __restrict__ X, __hip_bfloat16* __restrict__ Y,
+    const __hip_bfloat16* __restrict__ X,
+    const __hip_bfloat16* __restrict__ RES, __hip_bfloat16* __restrict__ Y,
     const float* __restrict__ gamma, const float* __restrict__ beta,
     float* __restrict__ rmean, float* __restrict__ rvar,
     float* __restrict__ smean, float* __restrict__ sinv,
@@ -178,9 +186,18 @@ __global__ __launch_bounds__(QUADS* P) void bn_onepass_fwd_kernel(
       if (g < S && row < M) {
         float v[4];
         bn_unpack4(raw[a][k], v);
+        if constexpr (RESID) {
+          float r[4];
+          bn_load4(RES + row * C + c, r);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          v[j] = bn_normalize(v[j], scale[j], shift[j], relu);
+          for (int j = 0; j < 4; ++j)
+            v[j] = bn_add_relu(bn_normalize(v[j], scale[j], shift[j], 0),
+                               r[j]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            v[j] = bn_normalize(v[j], scale[j], shift[j], relu);
+        }
         bn_store4(Y + row * C + c, v);
       }
     }
@@ -188,10 +205,12 @@ __global__ __launch_bounds__(QUADS* P) void bn_onepass_fwd_kernel(
 }
 
 // --------------------------------------------------------------- backward
-template <int QUADS, int P, int SPT, int RPS>
+template <int QUADS, int P, int SPT, int RPS, bool RESID>
 __global__ __launch_bounds__(QUADS* P) void bn_onepass_bwd_kernel(
     const __hip_bfloat16* __restrict__ X,
-    const __hip_bfloat16* __restrict__ DY, __hip_bfloat16* __restrict__ DX,
+    const __hip_bfloat16* __restrict__ DY,
+    const __hip_bfloat16* __restrict__ Z, __hip_bfloat16* __restrict__ DRES,
+    __hip_bfloat16* __restrict__ DX,
     const float* __restrict__ gamma, const float* __restrict__ beta,
     const float* __restrict__ smean, const float* __restrict__ sinv,
     float* __restrict__ dgamma, float* __restrict__ dbeta, int64_t M, int C,
@@ -224,6 +243,14 @@ __global__ __launch_bounds__(QUADS* P) void bn_onepass_bwd_kernel(
       if (g < S && row < M) {
         rx[a][k] = *reinterpret_cast<const ushort4*>(X + row * C + c);
         rdy[a][k] = *reinterpret_cast<const ushort4*>(DY + row * C + c);
+        if constexpr (RESID) {
+          // the ReLU behind the add masks dy as it arrives; the masked value
+          // is the identity branch's gradient
+          rdy[a][k] = bn_relu_mask4(
+              rdy[a][k], *reinterpret_cast<const ushort4*>(Z + row * C + c));
+          if (DRES != nullptr)
+            *reinterpret_cast<ushort4*>(DRES + row * C + c) = rdy[a][k];
+        }
       }
     }
   }
@@ -370,6 +397,60 @@ extern "C" int flreid_bn_onepass_config(int64_t M, int C) {
   return (f < 0 || b < 0) ? -1 : f;
 }
 
+// RESID picks the residual instantiation: res (forward) and z (backward) are
+// then read, and the BN's own ReLU is off.
+template <bool RESID>
+static void bn_op_launch_fwd(const void* X, const void* RES, void* Y,
+                             const float* gamma, const float* beta,
+                             float* rmean, float* rvar, float* smean,
+                             float* sinv, unsigned long long* nbt, int64_t M,
+                             int C, float momentum, float eps, float unbiased,
+                             int relu, int variant, hipStream_t stream) {
+  int cfg, swz;
+  bn_op_resolve(variant, kBnOpPrefFwd, M, C, &cfg, &swz);
+  const int nslab = bn_nslab(M, C);
+  switch (cfg) {
+#define BN_OP_CASE(id, Q, P, SPT, RPS)                                        \
+  case id:                                                                    \
+    hipLaunchKernelGGL((bn_onepass_fwd_kernel<Q, P, SPT, RPS, RESID>),        \
+                       dim3(C / (Q * 4)), dim3(Q * P), 0, stream,             \
+                       (const __hip_bfloat16*)X, (const __hip_bfloat16*)RES,  \
+                       (__hip_bfloat16*)Y, gamma, beta, rmean, rvar, smean,   \
+                       sinv, nbt, M, C, nslab, momentum, eps, unbiased, relu, \
+                       swz);                                                  \
+    break;
+    BN_OP_CFGS(BN_OP_CASE)
+#undef BN_OP_CASE
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+template <bool RESID>
+static void bn_op_launch_bwd(const void* X, const void* DY, const void* Z,
+                             void* DRES, void* DX, const float* gamma,
+                             const float* beta, const float* smean,
+                             const float* sinv, float* dgamma, float* dbeta,
+                             int64_t M, int C, int relu, int variant,
+                             hipStream_t stream) {
+  int cfg, swz;
+  bn_op_resolve(variant, kBnOpPrefBwd, M, C, &cfg, &swz);
+  const int nslab = bn_nslab(M, C);
+  switch (cfg) {
+#define BN_OP_CASE(id, Q, P, SPT, RPS)                                        \
+  case id:                                                                    \
+    hipLaunchKernelGGL((bn_onepass_bwd_kernel<Q, P, SPT, RPS, RESID>),        \
+                       dim3(C / (Q * 4)), dim3(Q * P), 0, stream,             \
+                       (const __hip_bfloat16*)X, (const __hip_bfloat16*)DY,   \
+                       (const __hip_bfloat16*)Z, (__hip_bfloat16*)DRES,       \
+                       (__hip_bfloat16*)DX, gamma, beta, smean, sinv, dgamma, \
+                       dbeta, M, C, nslab, relu, swz);                        \
+    break;
+    BN_OP_CFGS(BN_OP_CASE)
+#undef BN_OP_CASE
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
 extern "C" void flreid_bn_onepass_fwd(const void* X, void* Y,
                                       const float* gamma, const float* beta,
                                       float* rmean, float* rvar, float* smean,
@@ -377,22 +458,9 @@ extern "C" void flreid_bn_onepass_fwd(const void* X, void* Y,
                                       int64_t M, int C, float momentum,
                                       float eps, float unbiased, int relu,
                                       int variant, hipStream_t stream) {
-  int cfg, swz;
-  bn_op_resolve(variant, kBnOpPrefFwd, M, C, &cfg, &swz);
-  const int nslab = bn_nslab(M, C);
-  switch (cfg) {
-#define BN_OP_CASE(id, Q, P, SPT, RPS)                                        \
-  case id:                                                                    \
-    hipLaunchKernelGGL((bn_onepass_fwd_kernel<Q, P, SPT, RPS>),               \
-                       dim3(C / (Q * 4)), dim3(Q * P), 0, stream,             \
-                       (const __hip_bfloat16*)X, (__hip_bfloat16*)Y,          \
-                       gamma, beta, rmean, rvar, smean, sinv, nbt, M, C,      \
-                       nslab, momentum, eps, unbiased, relu, swz);            \
-    break;
-    BN_OP_CFGS(BN_OP_CASE)
-#undef BN_OP_CASE
-  }
-  HIP_CHECK(hipGetLastError());
+  bn_op_launch_fwd<false>(X, nullptr, Y, gamma, beta, rmean, rvar, smean, sinv,
+                          nbt, M, C, momentum, eps, unbiased, relu, variant,
+                          stream);
 }
 
 extern "C" void flreid_bn_onepass_bwd(const void* X, const void* DY, void* DX,
@@ -401,23 +469,30 @@ extern "C" void flreid_bn_onepass_bwd(const void* X, const void* DY, void* DX,
                                       float* dgamma, float* dbeta, int64_t M,
                                       int C, int relu, int variant,
                                       hipStream_t stream) {
-  int cfg, swz;
-  bn_op_resolve(variant, kBnOpPrefBwd, M, C, &cfg, &swz);
-  const int nslab = bn_nslab(M, C);
-  switch (cfg) {
-#define BN_OP_CASE(id, Q, P, SPT, RPS)                                        \
-  case id:                                                                    \
-    hipLaunchKernelGGL((bn_onepass_bwd_kernel<Q, P, SPT, RPS>),               \
-                       dim3(C / (Q * 4)), dim3(Q * P), 0, stream,             \
-                       (const __hip_bfloat16*)X,                              \
-                       (const __hip_bfloat16*)DY, (__hip_bfloat16*)DX, gamma, \
-                       beta, smean, sinv, dgamma, dbeta, M, C, nslab, relu,   \
-                       swz);                                                  \
-    break;
-    BN_OP_CFGS(BN_OP_CASE)
-#undef BN_OP_CASE
-  }
-  HIP_CHECK(hipGetLastError());
+  bn_op_launch_bwd<false>(X, DY, nullptr, nullptr, DX, gamma, beta, smean,
+                          sinv, dgamma, dbeta, M, C, relu, variant, stream);
+}
+
+extern "C" void flreid_bn_onepass_res_fwd(
+    const void* X, const void* RES, void* Y, const float* gamma,
+    const float* beta, float* rmean, float* rvar, float* smean, float* sinv,
+    unsigned long long* nbt, int64_t M, int C, float momentum, float eps,
+    float unbiased, int variant, hipStream_t stream) {
+  if (RES == nullptr)
+    throw std::invalid_argument("bn_onepass_res_fwd: no residual");
+  bn_op_launch_fwd<true>(X, RES, Y, gamma, beta, rmean, rvar, smean, sinv, nbt,
+                         M, C, momentum, eps, unbiased, 0, variant, stream);
+}
+
+extern "C" void flreid_bn_onepass_res_bwd(
+    const void* X, const void* DZ, const void* Z, void* DRES, void* DX,
+    const float* gamma, const float* beta, const float* smean,
+    const float* sinv, float* dgamma, float* dbeta, int64_t M, int C,
+    int variant, hipStream_t stream) {
+  if (Z == nullptr)
+    throw std::invalid_argument("bn_onepass_res_bwd: no saved output");
+  bn_op_launch_bwd<true>(X, DZ, Z, DRES, DX, gamma, beta, smean, sinv, dgamma,
+                         dbeta, M, C, 0, variant, stream);
 }
 
 }  // namespace flreid

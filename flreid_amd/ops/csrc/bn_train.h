@@ -138,6 +138,32 @@ __device__ __forceinline__ float bn_normalize(float v, float scale,
   return v;
 }
 
+// ---- residual epilogue -----------------------------------------------------
+// relu(bn(x) + res) as the three-kernel chain forms it: the BN output rounded
+// to bf16, the add in fp32 rounded to bf16, the ReLU last.
+__device__ __forceinline__ float bn_round_bf16(float v) {
+  return __bfloat162float(__float2bfloat16(v));
+}
+
+__device__ __forceinline__ float bn_add_relu(float y, float res) {
+#pragma clang fp contract(off)
+  const float z = bn_round_bf16(bn_round_bf16(y) + res);
+  return fmaxf(z, 0.f);
+}
+
+// threshold_backward on raw bf16 quads: dz where z > 0, +0 where z <= 0
+__device__ __forceinline__ ushort4 bn_relu_mask4(const ushort4 dz,
+                                                 const ushort4 z) {
+  float zf[4];
+  bn_unpack4(z, zf);
+  ushort4 d;
+  d.x = zf[0] <= 0.f ? (unsigned short)0 : dz.x;
+  d.y = zf[1] <= 0.f ? (unsigned short)0 : dz.y;
+  d.z = zf[2] <= 0.f ? (unsigned short)0 : dz.z;
+  d.w = zf[3] <= 0.f ? (unsigned short)0 : dz.w;
+  return d;
+}
+
 // Σ/M of the two backward sums
 __device__ __forceinline__ void bn_bwd_means(float tdy, float tdyx, int64_t M,
                                              float& mdy, float& mdyx) {

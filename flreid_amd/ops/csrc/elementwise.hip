@@ -14,6 +14,10 @@
 //
 // All kernels: fp32 compute; bf16 or fp32 I/O.
 
+#include <initializer_list>
+#include <stdexcept>
+
+#include "bn_train.h"
 #include "common.h"
 #include "ops.h"
 
@@ -286,12 +290,46 @@ extern "C" void flreid_importance(float* F, const void* g, int64_t numel,
 // --------------------------------------------------------------------------
 // eval-mode BatchNorm2d: y = (x − μ[c])·rsqrt(σ²[c]+eps)·γ[c] + β[c]
 // One bandwidth-bound pass (MIOpen's inference kernel measured ~0.3 TB/s on
-// ReID shapes; this is a plain coalesced elementwise).  layout 0 = NCHW
-// (c = i/(HW) % C), 1 = NHWC/channels-last (c = i % C).
+// ReID shapes).  layout 0 = NCHW (c = i/(HW) % C), 1 = NHWC/channels-last
+// (c = i % C).  With a residual the pass also does the block's
+// relu(y + identity): y rounded to the tensor dtype, the add in fp32, rounded,
+// ReLU last — the bits of the add and clamp kernels it replaces.
+//
+// Two kernels, one expression (bn_eval_value): one element per thread for any
+// layout, and for NHWC with C % 8 == 0 and 16-byte-aligned pointers one
+// 16-byte load per operand and one 16-byte store per thread (8 bf16 / 4 fp32
+// consecutive channels of one row).
 // --------------------------------------------------------------------------
 
-template <typename T, bool NHWC>
-__global__ void bn_eval_kernel(const T* __restrict__ x, T* __restrict__ y,
+// The form the one-element kernel has always compiled to, written out so that
+// it cannot move with the surrounding code: t = (x − μ)·inv, then one fma.
+__device__ __forceinline__ float bn_eval_value(float x, float mean, float var,
+                                               float gamma, float beta,
+                                               float eps) {
+#pragma clang fp contract(off)
+  const float inv = __frsqrt_rn(var + eps);
+  const float t = (x - mean) * inv;
+  return __builtin_fmaf(t, gamma, beta);
+}
+
+template <typename T>
+__device__ __forceinline__ float bn_eval_add_relu(float v, float r);
+
+template <>
+__device__ __forceinline__ float bn_eval_add_relu<float>(float v, float r) {
+#pragma clang fp contract(off)
+  return fmaxf(v + r, 0.f);
+}
+
+template <>
+__device__ __forceinline__ float bn_eval_add_relu<__hip_bfloat16>(float v,
+                                                                  float r) {
+  return bn_add_relu(v, r);
+}
+
+template <typename T, bool NHWC, bool RESID>
+__global__ void bn_eval_kernel(const T* __restrict__ x,
+                               const T* __restrict__ res, T* __restrict__ y,
                                const float* __restrict__ gamma,
                                const float* __restrict__ beta,
                                const float* __restrict__ mean,
@@ -300,10 +338,160 @@ __global__ void bn_eval_kernel(const T* __restrict__ x, T* __restrict__ y,
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= numel) return;
   const int c = NHWC ? (int)(i % C) : (int)((i / HW) % C);
-  const float inv = __frsqrt_rn(var[c] + eps);
-  float v = (load_as_float(x, i) - mean[c]) * inv * gamma[c] + beta[c];
-  if (relu) v = fmaxf(v, 0.f);
+  float v = bn_eval_value(load_as_float(x, i), mean[c], var[c], gamma[c],
+                          beta[c], eps);
+  if constexpr (RESID) {
+    v = bn_eval_add_relu<T>(v, load_as_float(res, i));
+  } else {
+    if (relu) v = fmaxf(v, 0.f);
+  }
   store_from_float(y, i, v);
+}
+
+// 16 bytes of T as floats
+template <typename T>
+struct BnEvalVec;
+
+template <>
+struct BnEvalVec<float> {
+  static constexpr int N = 4;
+  static __device__ __forceinline__ void load(const float* p, float v[N]) {
+    bn_load4(p, v);
+  }
+  static __device__ __forceinline__ void store(float* p, const float v[N]) {
+    bn_store4(p, v);
+  }
+};
+
+template <>
+struct BnEvalVec<__hip_bfloat16> {
+  static constexpr int N = 8;
+  static __device__ __forceinline__ void load(const __hip_bfloat16* p,
+                                              float v[N]) {
+    const uint4 t = *reinterpret_cast<const uint4*>(p);
+    const unsigned w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const unsigned short lo = (unsigned short)(w[k] & 0xffffu);
+      const unsigned short hi = (unsigned short)(w[k] >> 16);
+      v[2 * k] = __bfloat162float(*(const __hip_bfloat16*)&lo);
+      v[2 * k + 1] = __bfloat162float(*(const __hip_bfloat16*)&hi);
+    }
+  }
+  static __device__ __forceinline__ void store(__hip_bfloat16* p,
+                                               const float v[N]) {
+    unsigned w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const __hip_bfloat16 lo = __float2bfloat16(v[2 * k]);
+      const __hip_bfloat16 hi = __float2bfloat16(v[2 * k + 1]);
+      w[k] = (unsigned)*(const unsigned short*)&lo |
+             ((unsigned)*(const unsigned short*)&hi << 16);
+    }
+    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+};
+
+// NHWC, C % 8 == 0 (so numel % N == 0 and a thread's N channels stay inside
+// one row and start at a multiple of 4), every pointer 16-byte aligned
+template <typename T, bool RESID>
+__global__ __launch_bounds__(256) void bn_eval_wide_kernel(
+    const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ mean, const float* __restrict__ var,
+    int64_t numel, int C, float eps, int relu) {
+  constexpr int N = BnEvalVec<T>::N;
+  const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * N;
+  if (e >= numel) return;
+  const int c = (int)(e % C);
+  float v[N], r[N];
+  BnEvalVec<T>::load(x + e, v);
+  if constexpr (RESID) BnEvalVec<T>::load(res + e, r);
+#pragma unroll
+  for (int k = 0; k < N; k += 4) {
+    float g[4], b[4], m[4], s[4];
+    bn_load4(gamma + c + k, g);
+    bn_load4(beta + c + k, b);
+    bn_load4(mean + c + k, m);
+    bn_load4(var + c + k, s);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float t = bn_eval_value(v[k + j], m[j], s[j], g[j], b[j], eps);
+      if constexpr (RESID) {
+        t = bn_eval_add_relu<T>(t, r[k + j]);
+      } else {
+        if (relu) t = fmaxf(t, 0.f);
+      }
+      v[k + j] = t;
+    }
+  }
+  BnEvalVec<T>::store(y + e, v);
+}
+
+static bool bn_eval_aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;
+  return true;
+}
+
+template <typename T, bool RESID>
+static void bn_eval_launch(const void* x, const void* res, void* y,
+                           const float* gamma, const float* beta,
+                           const float* mean, const float* var, int64_t numel,
+                           int C, int64_t HW, float eps, int nhwc, int relu,
+                           int wide, hipStream_t stream) {
+  constexpr int BLOCK = 256;
+  const T* xp = (const T*)x;
+  const T* rp = (const T*)res;
+  T* yp = (T*)y;
+  if (wide && nhwc && C % 8 == 0 &&
+      bn_eval_aligned16({x, res, y, gamma, beta, mean, var})) {
+    const int64_t threads = numel / BnEvalVec<T>::N;
+    dim3 grid((unsigned)((threads + BLOCK - 1) / BLOCK)), block(BLOCK);
+    hipLaunchKernelGGL((bn_eval_wide_kernel<T, RESID>), grid, block, 0, stream,
+                       xp, rp, yp, gamma, beta, mean, var, numel, C, eps,
+                       relu);
+    return;
+  }
+  dim3 grid((unsigned)((numel + BLOCK - 1) / BLOCK)), block(BLOCK);
+  if (nhwc)
+    hipLaunchKernelGGL((bn_eval_kernel<T, true, RESID>), grid, block, 0,
+                       stream, xp, rp, yp, gamma, beta, mean, var, numel, C,
+                       HW, eps, relu);
+  else
+    hipLaunchKernelGGL((bn_eval_kernel<T, false, RESID>), grid, block, 0,
+                       stream, xp, rp, yp, gamma, beta, mean, var, numel, C,
+                       HW, eps, relu);
+}
+
+extern "C" void flreid_bn_eval_res(const void* x, const void* res, void* y,
+                                   const float* gamma, const float* beta,
+                                   const float* mean, const float* var,
+                                   int64_t numel, int C, int64_t HW, float eps,
+                                   int nhwc, int relu, int wide, int dtype,
+                                   hipStream_t stream) {
+  if (numel <= 0) return;
+  if (res != nullptr && relu)
+    throw std::invalid_argument(
+        "bn_eval: a residual implies the ReLU; relu must be 0");
+  if (dtype == kF32) {
+    if (res != nullptr)
+      bn_eval_launch<float, true>(x, res, y, gamma, beta, mean, var, numel, C,
+                                  HW, eps, nhwc, relu, wide, stream);
+    else
+      bn_eval_launch<float, false>(x, res, y, gamma, beta, mean, var, numel, C,
+                                   HW, eps, nhwc, relu, wide, stream);
+  } else {
+    if (res != nullptr)
+      bn_eval_launch<__hip_bfloat16, true>(x, res, y, gamma, beta, mean, var,
+                                           numel, C, HW, eps, nhwc, relu, wide,
+                                           stream);
+    else
+      bn_eval_launch<__hip_bfloat16, false>(x, res, y, gamma, beta, mean, var,
+                                            numel, C, HW, eps, nhwc, relu,
+                                            wide, stream);
+  }
+  HIP_CHECK(hipGetLastError());
 }
 
 extern "C" void flreid_bn_eval(const void* x, void* y, const float* gamma,
@@ -311,30 +499,8 @@ extern "C" void flreid_bn_eval(const void* x, void* y, const float* gamma,
                                const float* var, int64_t numel, int C,
                                int64_t HW, float eps, int nhwc, int relu,
                                int dtype, hipStream_t stream) {
-  constexpr int BLOCK = 256;
-  dim3 grid((unsigned)((numel + BLOCK - 1) / BLOCK)), block(BLOCK);
-  if (dtype == kF32) {
-    if (nhwc)
-      hipLaunchKernelGGL((bn_eval_kernel<float, true>), grid, block, 0, stream,
-                         (const float*)x, (float*)y, gamma, beta, mean, var,
-                         numel, C, HW, eps, relu);
-    else
-      hipLaunchKernelGGL((bn_eval_kernel<float, false>), grid, block, 0,
-                         stream, (const float*)x, (float*)y, gamma, beta, mean,
-                         var, numel, C, HW, eps, relu);
-  } else {
-    if (nhwc)
-      hipLaunchKernelGGL((bn_eval_kernel<__hip_bfloat16, true>), grid, block,
-                         0, stream, (const __hip_bfloat16*)x,
-                         (__hip_bfloat16*)y, gamma, beta, mean, var, numel, C,
-                         HW, eps, relu);
-    else
-      hipLaunchKernelGGL((bn_eval_kernel<__hip_bfloat16, false>), grid, block,
-                         0, stream, (const __hip_bfloat16*)x,
-                         (__hip_bfloat16*)y, gamma, beta, mean, var, numel, C,
-                         HW, eps, relu);
-  }
-  HIP_CHECK(hipGetLastError());
+  flreid_bn_eval_res(x, nullptr, y, gamma, beta, mean, var, numel, C, HW, eps,
+                     nhwc, relu, 1, dtype, stream);
 }
 
 }  // namespace flreid

@@ -45,6 +45,7 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(ce_smooth);
   FLREID_DEF(compose2);
   FLREID_DEF(bn_eval);
+  FLREID_DEF(bn_eval_res);
   FLREID_DEF(pairwise);
   FLREID_DEF(rowsq);
   FLREID_DEF(window_attn_fwd);
@@ -73,6 +74,8 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(bn_onepass_config);
   FLREID_DEF(bn_onepass_fwd);
   FLREID_DEF(bn_onepass_bwd);
+  FLREID_DEF(bn_onepass_res_fwd);
+  FLREID_DEF(bn_onepass_res_bwd);
   FLREID_DEF(drift_fwd);
   FLREID_DEF(drift_bwd);
   FLREID_DEF(kd_fwd);

@@ -38,6 +38,17 @@ void flreid_bn_eval(const void* x, void* y, const float* gamma,
                     const float* beta, const float* mean, const float* var,
                     int64_t numel, int C, int64_t HW, float eps, int nhwc,
                     int relu, int dtype, hipStream_t stream);
+// bn_eval with an optional residual (x's shape, layout and dtype; null for
+// none): y = relu(bn(x) + res), the BN output rounded to the tensor dtype
+// before the add; a residual implies the ReLU.  wide != 0 lets NHWC input
+// with C % 8 == 0 and 16-byte-aligned pointers take the 16-byte kernel (same
+// bits); wide == 0 keeps the one-element-per-thread kernel.  bn_eval itself
+// is this with no residual and wide = 1.
+void flreid_bn_eval_res(const void* x, const void* res, void* y,
+                        const float* gamma, const float* beta,
+                        const float* mean, const float* var, int64_t numel,
+                        int C, int64_t HW, float eps, int nhwc, int relu,
+                        int wide, int dtype, hipStream_t stream);
 
 // ---- distance.hip ---------------------------------------------------------
 void flreid_pairwise(const float* A, const float* B, const float* aa,
@@ -182,6 +193,23 @@ void flreid_bn_onepass_bwd(const void* x, const void* dy, void* dx,
                            const float* smean, const float* sinv,
                            float* dgamma, float* dbeta, int64_t M, int C,
                            int relu, int variant, hipStream_t stream);
+// The same with the residual epilogue, y = relu(bf16(bn(x)) + res): res and z
+// (the saved y) have x's shape and layout.  Backward masks dz where z <= 0,
+// writes the masked value to dres (the residual's gradient; may be null) and
+// runs the plain backward on it.  The BN's own ReLU does not combine.
+void flreid_bn_onepass_res_fwd(const void* x, const void* res, void* y,
+                               const float* gamma, const float* beta,
+                               float* rmean, float* rvar, float* smean,
+                               float* sinv, unsigned long long* nbt, int64_t M,
+                               int C, float momentum, float eps,
+                               float unbiased, int variant,
+                               hipStream_t stream);
+void flreid_bn_onepass_res_bwd(const void* x, const void* dz, const void* z,
+                               void* dres, void* dx, const float* gamma,
+                               const float* beta, const float* smean,
+                               const float* sinv, float* dgamma, float* dbeta,
+                               int64_t M, int C, int variant,
+                               hipStream_t stream);
 
 // ---- drift.hip ------------------------------------------------------------
 // ptrs: [n][2] int64 (p, anchor); chunks: [n_chunks][4] int32
