@@ -596,6 +596,54 @@ def bench_rank_stats(results, n):
         del qf, gf, sims
 
 
+def bench_triplet(results, n):
+    """K5b: triplet loss forward + backward in the seven modes that
+    triplet_gram.hip serves, at 64×2048 and 128×2048 (P×4 labels, squared
+    distances of about 4), the gram route against the eager chain
+    (FLREID_TRIPLET=eager) in one process, the two alternating.  One sample
+    is the mean time of `calls` back-to-back forward + backward calls around
+    a synchronise; reported are the median and the min / max over the
+    samples, in ms per call."""
+    reps, calls = (1, 1) if n == 1 else (7, 100)
+    modes = [(nf, hm, m) for nf in (False, True) for hm in (True, False)
+             for m in (0.3, None) if (nf, hm, m) != (False, True, 0.3)]
+    for N in (64, 128):
+        gen = torch.Generator().manual_seed(N)
+        feat = (torch.randn(N, 2048, generator=gen) * (2.0 / 2048) ** 0.5
+                ).cuda().requires_grad_(True)
+        labels = (torch.arange(N) // 4)[torch.randperm(N, generator=gen)].cuda()
+        for nf, hm, m in modes:
+            assert ops.triplet_loss_route(N, 2048, nf, hm, m, True) == "gram"
+
+            def sample(route):
+                if route == "eager":
+                    os.environ["FLREID_TRIPLET"] = "eager"
+                try:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(calls):
+                        ops.triplet_loss(feat, labels, m, nf, hm).backward()
+                        feat.grad = None
+                    torch.cuda.synchronize()
+                    return (time.perf_counter() - t0) / calls * 1e3
+                finally:
+                    os.environ.pop("FLREID_TRIPLET", None)
+
+            ms = {"gram": [], "eager": []}
+            for rep in range(reps + 2):                # two warm-up rounds
+                for route in ms:
+                    t = sample(route)
+                    if rep >= 2 or reps == 1:
+                        ms[route].append(t)
+            tag = (f"triplet_n{N}_{'cos' if nf else 'euc'}_"
+                   f"{'hard' if hm else 'wtd'}_{'hinge' if m else 'soft'}")
+            for route, v in ms.items():
+                v.sort()
+                results[f"{tag}_{route}"] = v[len(v) // 2]
+                results[f"{tag}_{route}_min"] = v[0]
+                results[f"{tag}_{route}_max"] = v[-1]
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
@@ -629,10 +677,18 @@ def main():
     p.add_argument("--rank-stats-only", action="store_true",
                    help="run only the CMC/mAP entry: rank-statistics kernel "
                         "against the torch sort chain")
+    p.add_argument("--triplet-only", action="store_true",
+                   help="run only the triplet entry: the Gram-form kernels "
+                        "against the eager chain, seven modes")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
+
+    if args.triplet_only:
+        bench_triplet(results, n)
+        report(results)
+        return
 
     if args.rank_stats_only:
         bench_rank_stats(results, n)

@@ -532,15 +532,95 @@ class _TripletHardFn(torch.autograd.Function):
         return grad, None, None, None
 
 
+def _ptr_or_null(t: Optional[torch.Tensor]) -> int:
+    return t.data_ptr() if t is not None else 0
+
+
+class _TripletGramFn(torch.autograd.Function):
+    """Triplet loss in Gram form (triplet_gram.hip): both metrics, both
+    minings, hinge or soft margin.  No host synchronisation in either
+    direction: the soft-margin mode's fallback to the 0.3 hinge is a device
+    select, and backward reads the upstream factor from device memory."""
+
+    @staticmethod
+    def forward(ctx, feature, target, margin, norm_feat, hard_mining, ext):
+        f = feature.detach().contiguous().float()
+        labels = target.contiguous()
+        n, d = f.shape
+        soft = margin is None or margin <= 0
+        dev = f.device
+
+        def buf(*shape):
+            return torch.empty(shape, device=dev, dtype=torch.float32)
+
+        slabs = buf(ext.triplet_gram_slices(n, d), n, n)
+        c, row_loss = buf(n, n), buf(n)
+        g, rinv = (buf(n, n), buf(n)) if norm_feat else (None, None)
+        c_fb, row_fb = (buf(n, n), buf(n)) if soft else (None, None)
+
+        ext.triplet_gram_fwd(f.data_ptr(), labels.data_ptr(),
+                             slabs.data_ptr(), _ptr_or_null(g),
+                             _ptr_or_null(rinv), c.data_ptr(),
+                             _ptr_or_null(c_fb), row_loss.data_ptr(),
+                             _ptr_or_null(row_fb), n, d, int(norm_feat),
+                             int(hard_mining), int(soft),
+                             0.0 if soft else float(margin), _stream())
+        loss, use_fb = row_loss.mean(), None
+        if soft:
+            overflow = loss == float("inf")
+            loss = torch.where(overflow, row_fb.mean(), loss)
+            use_fb = overflow.to(torch.int32)
+        ctx.save_for_backward(f, c, c_fb, use_fb, g, rinv)
+        ctx.ext = ext
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        f, c, c_fb, use_fb, g, rinv = ctx.saved_tensors
+        n, d = f.shape
+        gscale = grad_out.detach().reshape(1).float().contiguous()
+        grad = torch.empty_like(f)
+        ctx.ext.triplet_gram_bwd(f.data_ptr(), c.data_ptr(),
+                                 _ptr_or_null(c_fb), _ptr_or_null(use_fb),
+                                 _ptr_or_null(g), _ptr_or_null(rinv),
+                                 gscale.data_ptr(), grad.data_ptr(), n, d,
+                                 int(g is not None), _stream())
+        return grad, None, None, None, None, None
+
+
+def triplet_loss_route(n: int, d: int, norm_feat: bool, hard_mining: bool,
+                       margin: Optional[float], device_is_cuda: bool) -> str:
+    """Which path computes the triplet loss of an [n, d] batch: "hard"
+    (triplet.hip: batch-hard, euclidean, margin > 0), "gram"
+    (triplet_gram.hip: the seven other modes, up to
+    `ext.triplet_gram_max_n()` rows) or "eager" (reference.triplet_loss: the
+    CPU, larger batches, FLREID_TRIPLET=eager)."""
+    if (not device_is_cuda or n < 1 or d < 1
+            or os.environ.get("FLREID_TRIPLET", "kernel") == "eager"):
+        return "eager"
+    ext = require_extension("triplet_loss")
+    if ext is None:
+        return "eager"
+    if hard_mining and not norm_feat and margin is not None and margin > 0:
+        return "hard"
+    return "gram" if n <= ext.triplet_gram_max_n() else "eager"
+
+
 def triplet_loss(feature: torch.Tensor, target: torch.Tensor,
                  margin: Optional[float] = 0.3, norm_feat: bool = False,
                  hard_mining: bool = True) -> torch.Tensor:
-    if (feature.is_cuda and hard_mining and not norm_feat
-            and margin is not None and margin > 0 and feature.dim() == 2):
-        ext = require_extension("triplet_fwd")
-        if ext is not None:
-            return _TripletHardFn.apply(feature.float(), target.long(),
-                                        margin, ext)
+    route = "eager"
+    if feature.dim() == 2:
+        route = triplet_loss_route(feature.shape[0], feature.shape[1],
+                                   norm_feat, hard_mining, margin,
+                                   feature.is_cuda)
+    if route == "hard":
+        return _TripletHardFn.apply(feature.float(), target.long(), margin,
+                                    require_extension("triplet_fwd"))
+    if route == "gram":
+        return _TripletGramFn.apply(feature.float(), target.long(), margin,
+                                    norm_feat, hard_mining,
+                                    require_extension("triplet_gram_fwd"))
     return ref.triplet_loss(feature, target, margin, norm_feat, hard_mining)
 
 

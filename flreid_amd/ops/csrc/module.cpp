@@ -60,6 +60,10 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(window_attn_map_bwd);
   FLREID_DEF(triplet_fwd);
   FLREID_DEF(triplet_bwd);
+  FLREID_DEF(triplet_gram_max_n);
+  FLREID_DEF(triplet_gram_slices);
+  FLREID_DEF(triplet_gram_fwd);
+  FLREID_DEF(triplet_gram_bwd);
   FLREID_DEF(adaptive_linear_fwd);
   FLREID_DEF(theta_linear_fwd);
   FLREID_DEF(conv3x3_fwd);

@@ -130,6 +130,33 @@ void flreid_triplet_bwd(const float* F, const float* row_loss,
                         const int* p_idx, const int* n_idx, float* grad, int N,
                         int D, float coeff, hipStream_t stream);
 
+// ---- triplet_gram.hip -----------------------------------------------------
+// host helper: the largest batch (rows) the Gram-form triplet loss serves
+int flreid_triplet_gram_max_n();
+// host helper: K slices of the Gram phase; slabs is [slices][N][N] fp32
+int flreid_triplet_gram_slices(int N, int D);
+// Triplet loss of fp32 F [N][D] (any D >= 1) and int64 labels [N], metric
+// cosine (1) or squared euclidean (0), mining batch-hard (hard = 1) or
+// softmax-weighted, row loss log1p(exp(ap - an)) (soft = 1) or a hinge at
+// margin > 0.  Outputs: row_loss [N] and C [N][N] = d(sum of row losses) /
+// d(distance); with soft = 1 also row_fb / C_fb, the same for the 0.3 hinge
+// the soft-margin mode falls back to (else unread, may be null); with
+// cosine = 1 also G [N][N] and rinv [N] for the backward (else unread).
+// slabs is uninitialised scratch.
+void flreid_triplet_gram_fwd(const float* F, const int64_t* labels,
+                             float* slabs, float* G, float* rinv, float* C,
+                             float* C_fb, float* row_loss, float* row_fb,
+                             int N, int D, int cosine, int hard, int soft,
+                             float margin, hipStream_t stream);
+// dF [N][D] = (*gscale / N)·M·F from the forward's outputs, every element
+// written once.  use_fb (one int32 on the device, or null with C_fb null)
+// != 0 selects C_fb.  gscale: device pointer to the upstream gradient.
+void flreid_triplet_gram_bwd(const float* F, const float* C,
+                             const float* C_fb, const int* use_fb,
+                             const float* G, const float* rinv,
+                             const float* gscale, float* dF, int N, int D,
+                             int cosine, hipStream_t stream);
+
 // ---- adaptive_gemm.hip ----------------------------------------------------
 void flreid_adaptive_linear_fwd(const void* X, const float* GW,
                                 const float* AW, const float* ATTEN,
