@@ -644,6 +644,58 @@ def bench_triplet(results, n):
                 results[f"{tag}_{route}_max"] = v[-1]
 
 
+def bench_add_ln(results, n):
+    """Residual add + LayerNorm (add_ln.hip) against the eager chain the Swin
+    block ran before (add, fp32 LayerNorm, bf16 cast) at the four stage
+    shapes of swin-tiny at batch 64: fp32 stream, bf16 branch, bf16 rows out,
+    γ / β with gradients.  Forward under no_grad and forward + backward (both
+    outputs receive a gradient), the two routes alternating in one process.
+    One sample is the mean time of `calls` back-to-back calls around a
+    synchronise; reported are the median and the min / max over the samples
+    in ms per call, and for the fused route the GB/s of the traffic it needs:
+    forward 4 + 2 + 4 + 2 B per element, backward 4 + 2 + 4 + 4 + 2 B."""
+    reps, calls = (1, 1) if n == 1 else (7, 20)
+    for rows, c in ((64 * 3136, 96), (64 * 784, 192), (64 * 196, 384),
+                    (64 * 49, 768)):
+        x = torch.randn(rows, c, device="cuda", requires_grad=True)
+        br = torch.randn(rows, c, device="cuda").bfloat16().requires_grad_(True)
+        w = torch.randn(c, device="cuda", requires_grad=True)
+        b = torch.randn(c, device="cuda", requires_grad=True)
+        ds = torch.randn(rows, c, device="cuda")
+        dy = torch.randn(rows, c, device="cuda").bfloat16()
+        assert ops.add_layer_norm_route(c, x.dtype, br.dtype,
+                                        dy.dtype) == "kernel"
+        fns = {"fused": ops.add_layer_norm, "eager": ref.add_layer_norm}
+
+        def sample(route, grad):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                with torch.set_grad_enabled(grad):
+                    s, y = fns[route](x, br, w, b, 1e-5, torch.bfloat16)
+                if grad:
+                    torch.autograd.backward([s, y], [ds, dy])
+                    x.grad = br.grad = w.grad = b.grad = None
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / calls * 1e3
+
+        for grad, kind, nbytes in ((False, "fwd", 12), (True, "fwdbwd", 28)):
+            ms = {"fused": [], "eager": []}
+            for rep in range(reps + 2):                # two warm-up rounds
+                for route in ms:
+                    t = sample(route, grad)
+                    if rep >= 2 or reps == 1:
+                        ms[route].append(t)
+            tag = f"add_ln_{rows}x{c}_{kind}"
+            for route, v in ms.items():
+                v.sort()
+                results[f"{tag}_{route}"] = v[len(v) // 2]
+                results[f"{tag}_{route}_min"] = v[0]
+                results[f"{tag}_{route}_max"] = v[-1]
+            results[f"{tag}_fused_GBps"] = round(
+                rows * c * nbytes / (results[f"{tag}_fused"] / 1e3) / 1e9, 0)
+
+
 def report(results):
     for k in sorted(results):
         v = results[k]
@@ -680,10 +732,19 @@ def main():
     p.add_argument("--triplet-only", action="store_true",
                    help="run only the triplet entry: the Gram-form kernels "
                         "against the eager chain, seven modes")
+    p.add_argument("--add-ln-only", action="store_true",
+                   help="run only the residual add + LayerNorm entry: the "
+                        "fused kernel against the eager chain, four Swin "
+                        "stage shapes")
     args = p.parse_args()
     n = 1 if args.once else 50
     assert torch.cuda.is_available() and ops.extension_available()
     results = {}
+
+    if args.add_ln_only:
+        bench_add_ln(results, n)
+        report(results)
+        return
 
     if args.triplet_only:
         bench_triplet(results, n)

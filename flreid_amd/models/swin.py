@@ -27,6 +27,11 @@ dqkv in the backward.  Everything else is split into q, k, v and goes through
 head dim up to 64 take the fused VALU kernel (window_attn.hip, fp32 or bf16),
 bf16 windows of 65..144 tokens at head dim 32 (144 tokens at 384² / window
 12) the MFMA kernel (window_attn_mfma.hip), the rest the eager chain.
+The row passes around the attention go through `ops.add_layer_norm`
+(add_ln.hip) on the GPU: `norm1`, and the residual add fused with `norm2`,
+each one pass that hands the next Linear its rows in the autocast dtype.
+Only a plain nn.LayerNorm takes that route, and FLREID_SWIN_ADD_LN=0 turns
+it off; the CPU runs the separate operations.
 Staged execution (`stage_of`/`run_stages`) mirrors models/resnet.py so
 FedSTIL's head-only training path works unchanged (stages: stem, layers.0-3,
 head).
@@ -34,6 +39,7 @@ head).
 
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -183,11 +189,30 @@ class SwinBlock(nn.Module):
                     dtype, drop_p, h, w, self.window_size,
                     self.shift) == "map")
 
+    @staticmethod
+    def _fused_norm(norm: nn.Module, x: torch.Tensor) -> bool:
+        """Whether `norm` (and the residual add in front of it) goes through
+        `ops.add_layer_norm`: a plain nn.LayerNorm on the GPU with the
+        extension built, unless FLREID_SWIN_ADD_LN=0.  The norms FedWeIT
+        swaps in compose their own weights and stay as they are."""
+        return (type(norm) is nn.LayerNorm and x.is_cuda
+                and ops.extension_available()
+                and os.environ.get("FLREID_SWIN_ADD_LN", "1") != "0")
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         h, w = self.input_resolution
         b, L, c = x.shape
         shortcut = x
-        x = self.norm1(x).view(b, h, w, c)
+        # the rows leave the fused norms in the dtype the next Linear reads
+        out_dtype = (torch.get_autocast_dtype("cuda")
+                     if x.is_cuda and torch.is_autocast_enabled("cuda")
+                     else None)
+        if self._fused_norm(self.norm1, x):
+            x = ops.add_layer_norm(x, None, self.norm1.weight,
+                                   self.norm1.bias, self.norm1.eps, out_dtype)
+        else:
+            x = self.norm1(x)
+        x = x.view(b, h, w, c)
         if self._on_the_map(x):
             # qkv and proj are per-token: roll, partition and their inverses
             # are addressing inside the kernel
@@ -202,8 +227,15 @@ class SwinBlock(nn.Module):
             if self.shift > 0:
                 x = torch.roll(x, shifts=(self.shift, self.shift),
                                dims=(1, 2))
-        x = shortcut + self.drop_path(x.view(b, L, c))
-        return x + self.drop_path(self.mlp(self.norm2(x)))
+        x = self.drop_path(x.view(b, L, c))
+        if self._fused_norm(self.norm2, x):
+            x, xn = ops.add_layer_norm(shortcut, x, self.norm2.weight,
+                                       self.norm2.bias, self.norm2.eps,
+                                       out_dtype)
+        else:
+            x = shortcut + x
+            xn = self.norm2(x)
+        return x + self.drop_path(self.mlp(xn))
 
 
 class PatchMerging(nn.Module):

@@ -1210,6 +1210,146 @@ def patch_merge_ln(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
     return _PatchMergeLNFn.apply(x, gamma, beta, H, W, eps)
 
 
+_ADD_LN_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def add_layer_norm_route(c: int, x_dtype, branch_dtype, out_dtype) -> str:
+    """Which path serves s = x + branch, y = LayerNorm(s) over a last dim of
+    c on the GPU with the extension built (operands contiguous, 16-byte
+    aligned, affine LayerNorm): "kernel" (add_ln.hip) or "eager".
+    branch_dtype is None without a branch; out_dtype is the dtype y leaves
+    in.  The kernel keeps s in x's dtype, so a branch that would promote the
+    sum (bf16 x, fp32 branch) stays eager."""
+    if (c % 8 == 0 and 8 <= c <= 1536 and x_dtype in _ADD_LN_DTYPES
+            and out_dtype in _ADD_LN_DTYPES
+            and (branch_dtype is None or (
+                branch_dtype in _ADD_LN_DTYPES
+                and torch.promote_types(x_dtype, branch_dtype) == x_dtype))):
+        return "kernel"
+    return "eager"
+
+
+def _add_ln_fwd_raw(ext, x, branch, gamma_c, beta_c, eps, y_dtype, stats):
+    c = x.shape[-1]
+    rows = x.numel() // c
+    y = torch.empty(x.shape, device=x.device, dtype=y_dtype)
+    s = torch.empty_like(x) if branch is not None else x
+    mean = rstd = None
+    if stats:
+        mean, rstd = torch.empty(2, rows, device=x.device,
+                                 dtype=torch.float32).unbind(0)
+    ext.add_ln_fwd(x.data_ptr(), _ptr_or_null(branch), gamma_c.data_ptr(),
+                   beta_c.data_ptr(), _ptr_or_null(s if branch is not None else None),
+                   y.data_ptr(), _ptr_or_null(mean), _ptr_or_null(rstd),
+                   rows, c, float(eps), _dt(x),
+                   _dt(branch if branch is not None else x), _dt(y),
+                   _stream())
+    return s, y, mean, rstd
+
+
+class _AddLayerNormFn(torch.autograd.Function):
+    """Residual add + LayerNorm (add_ln.hip): (s, y) from (x, branch), or y
+    alone from x.  Saves s, mean and rstd; the backward adds the gradient
+    that reaches s directly to the LayerNorm's in the same pass, writes it
+    once per operand dtype and, only when gamma or beta require a gradient,
+    one dgamma / dbeta partial per block."""
+
+    @staticmethod
+    def forward(ctx, x, branch, gamma, beta, eps, y_dtype):
+        ctx.set_materialize_grads(False)
+        ext = require_extension("add_ln_fwd")
+        gamma_c = gamma.detach().float().contiguous()
+        beta_c = beta.detach().float().contiguous()
+        s, y, mean, rstd = _add_ln_fwd_raw(
+            ext, x.detach(), None if branch is None else branch.detach(),
+            gamma_c, beta_c, eps, y_dtype, True)
+        ctx.save_for_backward(s, gamma_c, mean, rstd)
+        ctx.branch_dtype = None if branch is None else branch.dtype
+        return y if branch is None else (s, y)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ds_in, dy = (None, grads[0]) if ctx.branch_dtype is None else grads
+        if ds_in is None and dy is None:
+            return None, None, None, None, None, None
+        ext = require_extension("add_ln_bwd")
+        s, gamma_c, mean, rstd = ctx.saved_tensors
+        c = s.shape[-1]
+        rows = s.numel() // c
+        if dy is not None:
+            dy = dy.contiguous()
+        if ds_in is not None:
+            ds_in = ds_in.contiguous()
+        ds = torch.empty_like(s)
+        ds_b = None
+        if (ctx.branch_dtype not in (None, s.dtype)
+                and ctx.needs_input_grad[1]):
+            ds_b = torch.empty(s.shape, device=s.device,
+                               dtype=ctx.branch_dtype)
+        affine = dy is not None and (ctx.needs_input_grad[2]
+                                     or ctx.needs_input_grad[3])
+        dg_part = db_part = None
+        if affine:
+            part = torch.empty(2, ext.add_ln_blocks(rows, c), c,
+                               device=s.device, dtype=torch.float32)
+            dg_part, db_part = part.unbind(0)
+        ext.add_ln_bwd(s.data_ptr(), gamma_c.data_ptr(), mean.data_ptr(),
+                       rstd.data_ptr(), _ptr_or_null(dy),
+                       _ptr_or_null(ds_in), ds.data_ptr(),
+                       _ptr_or_null(ds_b), _ptr_or_null(dg_part),
+                       _ptr_or_null(db_part), rows, c, _dt(s),
+                       _dt(ds_b if ds_b is not None else s),
+                       _dt(dy if dy is not None else s), int(affine),
+                       _stream())
+        dbranch = None
+        if ctx.branch_dtype is not None and ctx.needs_input_grad[1]:
+            dbranch = ds if ds_b is None else ds_b
+        dgamma = dbeta = None
+        if affine:
+            # torch's sum has a fixed order: the same bits every run
+            dgamma, dbeta = part.sum(1).unbind(0)
+        return ds, dbranch, dgamma, dbeta, None, None
+
+
+def add_layer_norm(x: torch.Tensor, branch: Optional[torch.Tensor],
+                   weight: Optional[torch.Tensor],
+                   bias: Optional[torch.Tensor], eps: float = 1e-5,
+                   out_dtype: Optional[torch.dtype] = None):
+    """s = x + branch, y = LayerNorm(s) over the last dim: (s, y), or y alone
+    when branch is None.  y leaves in out_dtype when one is given (what the
+    next GEMM reads under autocast), otherwise in the dtype F.layer_norm
+    would give it.  On the GPU with the extension built, contiguous 16-byte
+    aligned operands inside `add_layer_norm_route`'s regime take add_ln.hip;
+    everything else is the eager composition of ops/reference.py."""
+    route = "eager"
+    if (x.is_cuda and extension_available() and weight is not None
+            and bias is not None and x.numel() > 0 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0
+            and weight.numel() == x.shape[-1] == bias.numel()
+            and (branch is None or (
+                branch.shape == x.shape and branch.is_contiguous()
+                and branch.device == x.device
+                and branch.data_ptr() % 16 == 0))):
+        y_dtype = out_dtype
+        if y_dtype is None:
+            y_dtype = (torch.float32 if torch.is_autocast_enabled("cuda")
+                       else x.dtype)
+        route = add_layer_norm_route(
+            x.shape[-1], x.dtype, None if branch is None else branch.dtype,
+            y_dtype)
+    if route == "eager":
+        return ref.add_layer_norm(x, branch, weight, bias, eps, out_dtype)
+    if not (torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad
+            for t in (x, branch, weight, bias))):
+        ext = require_extension("add_ln_fwd")
+        s, y, _, _ = _add_ln_fwd_raw(
+            ext, x, branch, weight.detach().float().contiguous(),
+            bias.detach().float().contiguous(), eps, y_dtype, False)
+        return y if branch is None else (s, y)
+    return _AddLayerNormFn.apply(x, branch, weight, bias, eps, y_dtype)
+
+
 def adaptive_linear_fwd(x: torch.Tensor, gw: torch.Tensor,
                         atten: Optional[torch.Tensor],
                         aw: Optional[torch.Tensor],

@@ -16,7 +16,7 @@ import tempfile
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_flreid_hip.so")
 
-SOURCES = ["module.cpp", "elementwise.hip", "distance.hip", "window_attn.hip", "window_attn_mfma.hip", "window_attn_qkv.hip", "window_attn_map.hip", "triplet.hip", "triplet_gram.hip", "adaptive_gemm.hip", "conv3x3.hip", "conv3x3_img.hip", "conv3x3_img_ldsw.hip", "bn_train.hip", "bn_onepass.hip", "drift.hip", "kd.hip", "patch_merge.hip", "decomposed.hip", "head_step.hip", "penalty.hip", "herding.hip", "rank_stats.hip"]
+SOURCES = ["module.cpp", "elementwise.hip", "distance.hip", "window_attn.hip", "window_attn_mfma.hip", "window_attn_qkv.hip", "window_attn_map.hip", "triplet.hip", "triplet_gram.hip", "adaptive_gemm.hip", "conv3x3.hip", "conv3x3_img.hip", "conv3x3_img_ldsw.hip", "bn_train.hip", "bn_onepass.hip", "drift.hip", "kd.hip", "patch_merge.hip", "add_ln.hip", "decomposed.hip", "head_step.hip", "penalty.hip", "herding.hip", "rank_stats.hip"]
 
 # Compiled on their own with the packed-fp32 instructions (v_pk_mul_f32 and
 # kin) switched off: their fp32 work sits on MFMA accumulator quads, which the

@@ -86,6 +86,9 @@ PYBIND11_MODULE(_flreid_hip, m) {
   FLREID_DEF(icarl_distill);
   FLREID_DEF(patch_merge_ln_fwd);
   FLREID_DEF(patch_merge_ln_bwd);
+  FLREID_DEF(add_ln_blocks);
+  FLREID_DEF(add_ln_fwd);
+  FLREID_DEF(add_ln_bwd);
   FLREID_DEF(decomposed_fwd);
   FLREID_DEF(decomposed_bwd);
   FLREID_DEF(head_step_chunk);

@@ -267,6 +267,30 @@ void flreid_patch_merge_ln_bwd(const void* x, const float* gamma,
                                float* db, int64_t rows, int C, int H, int W,
                                int dtype, hipStream_t stream);
 
+// ---- add_ln.hip -----------------------------------------------------------
+// Residual add + LayerNorm over rows × C contiguous rows, C % 8 == 0,
+// 8 <= C <= 1536, every pointer 16-byte aligned; dtype tags are kF32 / kBF16.
+// host helper: blocks either launch uses for (rows, C), at most 1024 (0 out
+// of regime); dg_part / db_part are [blocks][C] fp32
+int flreid_add_ln_blocks(int64_t rows, int C);
+// s = a + b rounded to a_dtype and stored (b null: s is a, nothing stored);
+// y = LN(s)·gamma + beta in y_dtype, statistics of the stored s in fp32, the
+// variance from centred values; mean / rstd [rows] may both be null.
+void flreid_add_ln_fwd(const void* a, const void* b, const float* gamma,
+                       const float* beta, void* s, void* y, float* mean,
+                       float* rstd, int64_t rows, int C, float eps,
+                       int a_dtype, int b_dtype, int y_dtype,
+                       hipStream_t stream);
+// ds = ds_in + LNbwd(dy) in a_dtype; dy (y_dtype) or ds_in (a_dtype) may be
+// null, ds_b (may be null) receives the same values in b_dtype.  affine != 0:
+// one dgamma / dbeta partial per block, no atomics, summed by the caller;
+// affine == 0 leaves dg_part / db_part (may be null) alone.
+void flreid_add_ln_bwd(const void* s, const float* gamma, const float* mean,
+                       const float* rstd, const void* dy, const void* ds_in,
+                       void* ds, void* ds_b, float* dg_part, float* db_part,
+                       int64_t rows, int C, int a_dtype, int b_dtype,
+                       int y_dtype, int affine, hipStream_t stream);
+
 // ---- decomposed.hip -------------------------------------------------------
 // host helper; out-parameters (tasks_per_row, blocks): dmask_part is
 // [rows][tasks_per_row], datten_part is [blocks][KB]

@@ -461,6 +461,23 @@ def window_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# residual add + LayerNorm (the row passes of a Swin block)
+# ---------------------------------------------------------------------------
+
+def add_layer_norm(x: torch.Tensor, branch: Optional[torch.Tensor],
+                   weight: Optional[torch.Tensor],
+                   bias: Optional[torch.Tensor], eps: float = 1e-5,
+                   out_dtype: Optional[torch.dtype] = None):
+    """s = x + branch, y = F.layer_norm(s) over the last dim, cast to
+    out_dtype when one is given: (s, y), or y alone when branch is None."""
+    s = x if branch is None else x + branch
+    y = F.layer_norm(s, (s.shape[-1],), weight, bias, eps)
+    if out_dtype is not None:
+        y = y.to(out_dtype)
+    return y if branch is None else (s, y)
+
+
+# ---------------------------------------------------------------------------
 # herding exemplar selection (ref:methods/icarl.py:97-139)
 # ---------------------------------------------------------------------------
 
